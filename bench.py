@@ -5,6 +5,10 @@ linearisation, structured IPM) followed by the device-side Euler step of ego and
 and the x_ref rule of Highway_env.step.  Inputs stay in HBM (torch tensors on cuda).
 Multi-GPU: one process per GPU, egos sharded (weak scaling), one RCCL all-reduce of the
 closed-loop statistics per episode.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line (roofline fields come from
+the timed steps' own HIP events).  --full adds the CPU baselines (host build of the kernels,
+NumPy oracle), measured after the timed steps; --dump-outputs DIR writes the last step's arrays.
 """
 from __future__ import annotations
 
@@ -172,6 +176,29 @@ def launch_ranks(a):
     sys.exit(subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, rank, first_ego, tensors):
+    """--dump-outputs: the buffers the last timed step left its caller -- the solve's uPred, J,
+    status and iteration count, the x / z / x_ref it solved for, the scene and the closed-loop
+    statistics, one row per ego of this rank -- as <path>/<name>.npy in float64 (rank r > 0 of
+    a multi-GPU run writes <name>.rank<r>.npy).  The population is seeded, so the same arguments
+    give the same inputs on every run and two builds compare array for array.  Above 64 MB in
+    all, a fixed seeded sample of the egos is written; ego.npy holds the global ego indices."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in tensors.items()}
+    B = next(iter(arrs.values())).shape[0]
+    per_ego = sum(v.nbytes // max(B, 1) for v in arrs.values()) + 8
+    keep = np.arange(B)
+    if B * per_ego > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(B, DUMP_MAX_BYTES // per_ego, replace=False))
+    arrs = {k: v[keep] for k, v in arrs.items()}
+    arrs["ego"] = (first_ego + keep).astype(np.float64)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + (".npy" if rank == 0 else f".rank{rank}.npy")), v)
+
+
 class _HostSimPlan:
     """TEST-ONLY backend of this script (BMPC_BENCH_BACKEND=hostsim): the host build of the
     kernel templates (tests/hostsim) behind the few BatchPlan calls the closed loop makes, on
@@ -231,9 +258,16 @@ def main():
                     help="highway CVaR closed loop: fused = the K steps of every ego in one k_loop launch "
                          "(bmpc_loop_device: the egos' loops are independent, so no step waits for the slowest "
                          "ego of the previous one); steps = k_env + k_tree + k_ipm launched per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-egos", type=int, default=4096, help="egos of the C++ host-build baseline sample")
-    ap.add_argument("--oracle-egos", type=int, default=16, help="egos of the NumPy-oracle baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the CPU "
+                         "baselines (host build of the kernels, NumPy oracle); a plain run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--cpu-egos", type=int, default=4096, help="egos of the C++ host-build baseline sample (--full)")
+    ap.add_argument("--oracle-egos", type=int, default=16, help="egos of the NumPy-oracle baseline sample (--full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left its caller (inputs and results of "
+                         "the last solve of this rank's egos) as DIR/<name>.npy, float64")
     ap.add_argument("--traffic", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -406,6 +440,9 @@ def main():
         iters_mean = float(st_loc[abi.ENVS_ITERS] / max(st_loc[abi.ENVS_SOLVES], 1))
     else:
         iters_mean = float(it_sum.sum().item()) / (B * max(a.steps, 1))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, lo,
+                     dict(upred=up, J=Jv, status=st, iters=it, x=tx, z=tz, xref=tr, scene=scene, stats=estats))
     total = G * a.steps
     value = total / elapsed
     if rank == 0:
@@ -478,7 +515,7 @@ def main():
         }
         if host:
             out["backend"] = "hostsim (TEST-ONLY host build over gloo: not a measurement)"
-        if not a.no_cpu_baseline and world == 1 and not (quad or robust) and not host:
+        if a.full and not a.no_cpu_baseline and world == 1 and not (quad or robust) and not host:
             cores, aff, quota = usable_cores()
             try:
                 cb = cpu_cxx_baseline(a.N, a.NB, min(a.cpu_egos, G), 3, cores)

@@ -44,3 +44,25 @@ def test_bench_two_ranks_self_launch_matches_one_rank():
         assert abs(c2[k] - c1[k]) <= 1e-9 * max(1.0, abs(c1[k])), (k, c2[k], c1[k])
     for k in ("infeasible", "collision_steps", "collided_egos", "any_collided"):
         assert c2[k] == c1[k], (k, c2[k], c1[k])
+
+
+def test_dump_outputs_writes_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs: one float64 array per buffer the last timed step left its caller, one row
+    per ego, identical from run to run with the same arguments (the population is seeded)."""
+    import numpy as np
+    common = ["--gpus", "1", "--N", "10", "--NB", "1", "--batch", "4", "--steps", "2", "--warmup", "1"]
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    line = _bench(*common, "--dump-outputs", a)
+    _bench(*common, "--dump-outputs", b)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["cpu_baseline"] is None
+    names = sorted(os.listdir(a))
+    assert names == sorted(n + ".npy" for n in ("upred", "J", "status", "iters", "x", "z", "xref", "scene",
+                                                 "stats", "ego"))
+    for n in names:
+        va, vb = np.load(os.path.join(a, n)), np.load(os.path.join(b, n))
+        assert va.dtype == np.float64 and va.shape[0] == 4 and np.all(np.isfinite(va)), n
+        assert np.array_equal(va, vb), n
+    assert np.load(os.path.join(a, "upred.npy")).shape[2] == 2
+    assert np.array_equal(np.load(os.path.join(a, "ego.npy")), np.arange(4.0))
+    # the statistics count the timed steps alone: --steps sets their number
+    assert line["closed_loop"]["solves"] == 4 * 2

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 
 
 class _HostPlan:
@@ -62,6 +62,7 @@ def host_device(monkeypatch):
     yield
 
 
+@needs_reference
 def test_reference_main_quadruped_runs_unchanged(host_device, monkeypatch):
     """main_quadruped.py (reference :1-48): Quad_constants from the star import (:31),
     BranchMPCProx, quadruped_env.sim(mpc) (:43) -- the scene loop is shortened to 2 s."""
@@ -79,6 +80,7 @@ def test_reference_main_quadruped_runs_unchanged(host_device, monkeypatch):
     assert len(xPred_rec[0]) == 6        # BT2array over the 2 + 4 non-root branches
 
 
+@needs_reference
 def test_reference_main_branch_runs_unchanged(host_device, monkeypatch):
     """main_branch.sim_overtake (reference :20-51): BranchMPC_CVaR with N=8, NB=2 in the
     overtake scene (Highway_env_branch.sim_overtake) -- shortened to 1 s."""
@@ -129,6 +131,7 @@ def test_bt_is_live_after_solve(host_device):
     assert mpc.BT is not first              # rebuilt for the new solve
 
 
+@needs_reference
 def test_reference_sim_merge_runs_unchanged(host_device, monkeypatch):
     """main_branch.sim_merge (reference :53-88): PredictiveModel_merge with linear
     interpolants, BranchMPC_CVaR(ralpha=0.1) taking S / bx every step, Highway_env_merge --
@@ -164,3 +167,54 @@ def test_reference_sim_merge_runs_unchanged(host_device, monkeypatch):
     np.testing.assert_allclose(state_rec[0][:9], g["traj_x"][1:10], atol=1e-2)
     np.testing.assert_allclose(input_rec[0][:10], g["traj_u"][:10], atol=2e-2)
     np.testing.assert_allclose(state_rec[1][:9], g["traj_z"][1:10], atol=1e-9)
+
+
+# ---- the same two scenes with no file outside the repository: the controllers built as
+# main_branch.py / main_quadruped.py build them (the set-up of tests/test_compat_gpu.py and
+# tests/test_compat_quad_gpu.py), on the host build, with the assertions of the tests above ----
+
+def test_overtake_scene_through_dropin_surface(host_device, monkeypatch):
+    import Highway_env_branch
+    import Init_MPC
+    import MPC_branch
+    from common import golden
+    from highway_branch_dyn import PredictiveModel, backup_brake, backup_lc, backup_maintain
+    from utils import Branch_constants
+    N, n, d, am, rm, dt, NB, N_lane = 8, 4, 2, 6.0, 0.3, 0.1, 2, 4
+    xRef = np.array([0.5, 1.8, 15, 0])
+    cons = Branch_constants(s1=2, s2=3, c2=0.5, tran_diag=0.3, alpha=1, R=1.2, am=am, rm=rm, J_c=20, s_c=1,
+                            ylb=0., yub=7.2, L=4, W=2.5, col_alpha=5, Kpsi=0.1)
+    backupcons = [lambda x: backup_maintain(x, cons), lambda x: backup_brake(x, cons), lambda x: backup_lc(x, xRef)]
+    model = PredictiveModel(n, d, N, backupcons, dt, cons)
+    mpc = MPC_branch.BranchMPC_CVaR(Init_MPC.initBranchMPC(n, d, N, NB, xRef, am, rm, N_lane, cons.W), model,
+                                    ralpha=0.9)
+    full_sim = Highway_env_branch.Highway_sim
+    monkeypatch.setattr(Highway_env_branch, "Highway_sim", lambda env, T: full_sim(env, 1.0))
+    rec = Highway_env_branch.sim_overtake(mpc, N_lane)
+    assert _HostPlan.solves == 10
+    state_rec, input_rec = rec[0], rec[1]
+    assert np.all(np.isfinite(state_rec))
+    assert np.all(np.abs(input_rec[0][:, 1]) <= rm + 1e-6)
+    g = golden("highway_n8_nb2")
+    assert np.all(g["traj_exit"][:10] == 0)
+    np.testing.assert_allclose(input_rec[0][:10], g["traj_u"][:10], atol=1e-6)
+    np.testing.assert_allclose(state_rec[0][:9], g["traj_x"][1:10], atol=1e-6)
+
+
+def test_quadruped_scene_through_dropin_surface(host_device):
+    import Init_MPC
+    import MPC_branch
+    import quadruped_env
+    from quadruped_branch_dyn import PredictiveModel, backup_forward, backup_stop
+    from utils import Quad_constants
+    dt, NB, vxm, vym, rm, v0, n, d, N = 0.2, 2, 0.2, 0.1, 0.5, 0.2, 3, 3, 25
+    cons = Quad_constants(s1=2, s2=3, c2=0.5, alpha=1, R=1.2, vxm=vxm, vym=vym, rm=rm, L1=0.5, W1=0.3, L2=1,
+                          W2=0.6, col_tol=0.2, col_alpha=5)
+    model = PredictiveModel(n, d, N, [lambda x: backup_forward(x, v0), lambda x: backup_stop(x)], dt, cons)
+    mpc = MPC_branch.BranchMPCProx(Init_MPC.initquadBranchMPC(n, d, N, NB, np.array([5., 5., 0.]), vxm, vym, rm),
+                                   model)
+    state_rec, input_rec, backup_rec, choice_rec, xPred_rec, zPred_rec = quadruped_env.sim(mpc, T=2.0)
+    assert _HostPlan.solves == 10
+    assert np.all(np.isfinite(state_rec)) and np.all(np.isfinite(input_rec))
+    assert np.all(np.abs(input_rec[0][:, 0]) <= vxm + 1e-6) and np.all(np.abs(input_rec[0][:, 2]) <= rm + 1e-6)
+    assert len(xPred_rec[0]) == 6

@@ -17,7 +17,7 @@ for v in base noeq; do
   echo "== $v config3" >> $o/equil_ab.log
   BMPC_LIBRARY=$L timeout -k 10 300 python tools/quick_bench.py 4096 30 2 2>&1 | grep "^step" | cut -c1-150 >> $o/equil_ab.log || exit $?
 done
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $o/bench.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/bench.log 2>&1 || exit $?
 BMPC_LIBRARY=belief-planning_amd/libbmpc_noeq.so timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_noeq.log 2>&1 || exit $?
 tail -n 1 $o/bench.log | cut -c1-400
 # per-phase bytes: the phase-per-kernel tools build (same arithmetic as the product kernel, bit for

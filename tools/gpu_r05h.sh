@@ -23,5 +23,5 @@ e = json.load(open(sys.argv[1])); p = "profiles/pmc_traffic.json"; d = json.load
 d = [x for x in d if not (x["key"] == e["key"] and x["source_hash"] == e["source_hash"])] + [e]
 json.dump(d, open(p, "w"), indent=1)
 PY
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${tag}_bench.log 2>&1 || exit $?
-cut -c1-200 $out; tail -n 1 gpurun_out/${tag}_bench.log | cut -c1-300
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $(dirname $out)/${tag}_bench.log 2>&1 || exit $?
+cut -c1-200 $out; tail -n 1 $(dirname $out)/${tag}_bench.log | cut -c1-300

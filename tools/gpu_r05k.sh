@@ -15,7 +15,7 @@ e = json.load(open(sys.argv[1])); p = "profiles/pmc_traffic.json"; d = json.load
 d = [x for x in d if not (x["key"] == e["key"] and x["source_hash"] == e["source_hash"])] + [e]
 json.dump(d, open(p, "w"), indent=1)
 PY
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $o/bench.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/bench.log 2>&1 || exit $?
 timeout -k 10 300 python bench.py --gpus 1 --global-batch 8192 --no-cpu-baseline > $o/bench_gb8192.log 2>&1 || exit $?
 out=$o/config_sweep.jsonl
 : > $out

@@ -11,5 +11,7 @@ mkdir -p gpurun_out/$tag
 timeout -k 10 900 python -u -m pytest tests -m gpu --maxfail=20 -q -rA --timeout 300 --timeout-method thread > gpurun_out/$tag/gpu_tests.log 2>&1
 rc=$?; [ $rc -ne 0 ] && [ $rc -ne 1 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$tag/smoke.log 2>&1 || exit $?
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/$tag/bench.log 2>&1 || exit $?
-tail -n 1 gpurun_out/$tag/bench.log | cut -c1-300
+logs=${BMPC_LOG_DIR:-logs}/$tag
+mkdir -p $logs
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $logs/bench.log 2>&1 || exit $?
+tail -n 1 $logs/bench.log | cut -c1-300
