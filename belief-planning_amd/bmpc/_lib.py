@@ -36,7 +36,8 @@ def sources():
     """Translation units of libbmpc.so: the C ABI + small kernels, one unit per predictive model's
     solver kernels (compiled in parallel), the host-side plan builders."""
     srcs = [os.path.join(CSRC, f) for f in ("bmpc_hip.hip", "bmpc_k_highway.hip", "bmpc_k_highway_t.hip",
-                                            "bmpc_k_merge.hip", "bmpc_k_quadruped.hip", "bmpc_kb_highway.hip",
+                                            "bmpc_k_merge.hip", "bmpc_k_merge_loop.hip", "bmpc_k_quadruped.hip",
+                                            "bmpc_kb_highway.hip",
                                             "bmpc_kb_highway_t.hip", "bmpc_kb_merge.hip", "bmpc_kb_quadruped.hip",
                                             "bmpc_plan.cpp", "bmpc_qpplan.cpp")]
     if _phased():
@@ -113,6 +114,7 @@ _SIGS = {
     "bmpc_set_robust_warm_start": (C.c_int, [C.c_void_p] * 5),
     "bmpc_set_transform": (C.c_int, [C.c_void_p] * 5),
     "bmpc_set_fx": (C.c_int, [C.c_void_p] * 3),
+    "bmpc_get_transform": (C.c_int, [C.c_void_p] * 4),
     "bmpc_get_branch_dp": (C.c_int, [C.c_void_p] * 2),
     "bmpc_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "bmpc_timing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -123,6 +125,9 @@ _SIGS = {
     "bmpc_hmm_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9),
     "bmpc_env_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10),
     "bmpc_loop_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "bmpc_set_merge_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3),
+    "bmpc_merge_env_step": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 10),
+    "bmpc_merge_loop_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
     "bmpc_qp_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
                       + [C.c_int, C.c_double] + [C.c_void_p] * 5),
 }

@@ -71,6 +71,25 @@ def make_env(n_lane=4, L=4.0, W=2.5, Kpsi=0.1, v0=20.0, target=(0.5, 1.8, 15.0, 
     return E
 
 
+ENV_MERGED = ENV_LANE0   # merge scene: "the ego has merged" (0 on the ramp)
+
+
+class MergeEnvDesc(C.Structure):
+    """bmpc_merge_env_desc: the sim_merge scene (Highway_env_branch.py:275-380)."""
+    _fields_ = [("n_lane", C.c_int32), ("merge_lane", C.c_int32), ("merge_s", C.c_double), ("W", C.c_double),
+                ("Kpsi", C.c_double), ("v0", C.c_double), ("psimax", C.c_double), ("vlen", C.c_double),
+                ("vwid", C.c_double)]
+
+
+def make_merge_env(n_lane=2, merge_lane=1, merge_s=50.0, W=2.5, Kpsi=0.1, v0=20.0, psimax=0.25, vlen=4.0, vwid=2.4):
+    """Scene constants of main_branch.sim_merge (main_branch.py:53-88): Branch_constants, the ramp
+    of merge_geometry(N_lane, 1, 50, 300), BranchMPC_CVaR.psimax, vehicle() size."""
+    E = MergeEnvDesc()
+    E.n_lane, E.merge_lane = int(n_lane), int(merge_lane)
+    E.merge_s, E.W, E.Kpsi, E.v0, E.psimax, E.vlen, E.vwid = merge_s, W, Kpsi, v0, psimax, vlen, vwid
+    return E
+
+
 def _fill(arr, values):
     v = np.asarray(values, dtype=np.float64).ravel()
     for i, x in enumerate(v):

@@ -112,6 +112,39 @@ class BatchPlan:
                                                      iters_ptr, stats_ptr, stream)]
         check(lib().bmpc_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_loop_device")
 
+    def set_merge_scene(self, env: abi.MergeEnvDesc, grid, refY, refpsi):
+        """The plan's sim_merge scene (bmpc_set_merge_scene): its constants and the ramp's lane
+        references refY(X), refpsi(X) over one grid.  HIGHWAY_MERGE CVaR plans."""
+        g, y, p = (np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1)) for a in (grid, refY, refpsi))
+        if not (g.size == y.size == p.size):
+            raise ValueError("grid, refY and refpsi must have one length")
+        check(lib().bmpc_set_merge_scene(self._h, C.byref(env), g.size, _p(g), _p(y), _p(p)), "bmpc_set_merge_scene")
+
+    def merge_env_step_device(self, t: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr=None,
+                              status_ptr=None, iters_ptr=None, stats_ptr=None, stream=None):
+        """One closed-loop sim_merge step of every ego on the device (bmpc_merge_env_step): Euler
+        steps, collision flag, lane flag, obstacle input -> the next solve's x, z, xref, and its S /
+        bx in the plan's transform slots (no set_transform before solve_device).  Async."""
+        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr,
+                                                     x_ptr, z_ptr, xref_ptr, stats_ptr, stream)]
+        check(lib().bmpc_merge_env_step(self._h, int(t), *vp), "bmpc_merge_env_step")
+
+    def merge_loop_device(self, t0: int, nsteps: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr,
+                          status_ptr, iters_ptr, stats_ptr=None, stream=None):
+        """nsteps closed-loop sim_merge steps of every ego (bmpc_merge_loop_device):
+        merge_env_step_device(t) then solve_device per step, the same results; one fused launch
+        (k_loop) when the batch takes the one-wave IPM.  Async on `stream`."""
+        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
+                                                     iters_ptr, stats_ptr, stream)]
+        check(lib().bmpc_merge_loop_device(self._h, int(t0), int(nsteps), *vp), "bmpc_merge_loop_device")
+
+    def get_transform(self):
+        """The S [B,n,n], bx [B,nFx] and (S on, bx set) flags [B,2] in the egos' transform slots."""
+        B, n, nF = self.batch, self.desc.n, self.desc.nFx
+        S, bx, fl = np.zeros((B, n, n)), np.zeros((B, nF)), np.zeros((B, 2))
+        check(lib().bmpc_get_transform(self._h, _p(S), _p(bx), _p(fl)), "bmpc_get_transform")
+        return dict(S=S, bx=bx, s_on=fl[:, 0] != 0, bx_set=fl[:, 1] != 0)
+
     def get_warm_start(self):
         """Checkpoint of the per-ego warm start (uLin, p, Jcons, OldInput)."""
         B, d = self.batch, self.desc.d

@@ -75,6 +75,78 @@ def xref_rule(x, z, v0=20.0):
     return xref, tgt
 
 
+def merge_desc(N=40, NB=1, N_lane=2, am=7.0, rm=0.3, L=4.0, W=2.5, s1=2.0, ralpha=0.1):
+    """main_branch.sim_merge (:53-88): initBranchMPC(4, 2, 40, 1, ..., N_lane=2) driving
+    BranchMPC_CVaR(ralpha=0.1) over PredictiveModel_merge's main-road model (pred_model[0])."""
+    Fx = np.array([[0., 1, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1], [0, 0, 0, -1]])
+    bx = np.array([N_lane * 3.6 - W / 2, -W / 2, 0.25, 0.25])
+    Fu = np.kron(np.eye(2), np.array([1, -1])).T
+    bu = np.array([am, am, rm, rm])
+    return abi.make_desc(abi.CTRL_CVAR, abi.MODEL_HIGHWAY_MERGE, 4, 2, N, NB, 2, 0.1,
+                         np.diag([0., 3, 3, 10]), np.diag([1., 100]), Fx, bx, Fu, bu, [0., 300.],
+                         [L, W, s1, float(N_lane)], ralpha=ralpha)
+
+
+def merge_policy_rows(B, Kpsi=0.1, v0=20.0):
+    """backupcons_normal of sim_merge (:83): maintain_trackV(v0), brake."""
+    return [[(abi.POL_MAINTAIN_TRACKV, (Kpsi, v0)), (abi.POL_BRAKE, (Kpsi,))] for _ in range(B)]
+
+
+def merge_lane_ref(N_lane=2, merge_lane=1, merge_s=50, merge_R=300, merge_side=0):
+    """The ramp's lane references (grid X, refY, refpsi) of sim_merge (:74-79), from the drop-in
+    module's merge_geometry."""
+    from Highway_env_branch import merge_geometry
+    X1, X2, Y1, Y2, p1, p2 = merge_geometry(N_lane, merge_lane, merge_s, merge_R, merge_side)
+    return np.append(X1, X2), np.append(Y1, Y2), np.append(p1, p2)
+
+
+MERGE_X0 = np.array([24., 13, 20, -0.2])   # Highway_env_merge's initial states (:312)
+MERGE_Z0 = np.array([15., 5.4, 20, 0])
+
+
+def seeded_merge_batch(B, seed=0):
+    """A Monte-Carlo population of merge episodes: row 0 is sim_merge's initial state, the others
+    start around it (ego +-2 m along / +-0.2 m across the ramp, +-1 m/s, +-0.02 rad; obstacle
+    +-3 m along its lane, +-1 m/s)."""
+    rng = np.random.default_rng(seed)
+    x = np.repeat(MERGE_X0[None], B, 0)
+    z = np.repeat(MERGE_Z0[None], B, 0)
+    x[1:] += rng.uniform(-1, 1, (B - 1, 4)) * [2, 0.2, 1, 0.02]
+    z[1:] += rng.uniform(-1, 1, (B - 1, 4)) * [3, 0, 1, 0]
+    return x, z
+
+
+def merge_population(B, steps, seed=0, device=0):
+    """`steps` closed-loop merge steps of B seeded episodes, resident on the GPU
+    (BatchPlan.merge_loop_device).  Returns the per-ego statistics rows [B, ENV_NSTAT] (the form
+    distributed.episode_stats takes; a step's solve is booked by the next step, so they cover
+    steps - 1 solves) and the final scene [B, ENV_STRIDE]."""
+    import torch
+    from . import plan
+    x, z = seeded_merge_batch(B, seed)
+    pl = plan.BatchPlan(merge_desc(), B, device)
+    pl.set_policies(merge_policy_rows(B))
+    pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
+    dev = torch.device("cuda", device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
+    scene[:, abi.ENV_X:abi.ENV_X + 4] = torch.tensor(x, **f64)
+    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = torch.tensor(z, **f64)
+    up = torch.zeros((B, pl.U, 2), **f64)
+    J = torch.zeros(B, **f64)
+    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
+    tx, tz, tr = (torch.zeros((B, 4), **f64) for _ in range(3))
+    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
+    stream = torch.cuda.Stream(dev)
+    pl.merge_loop_device(0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(), tr.data_ptr(),
+                         J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    out = stats.cpu().numpy(), scene.cpu().numpy()
+    pl.close()
+    return out
+
+
 def quadruped_desc(N=25, NB=2, vxm=0.2, vym=0.1, rm=0.5, dt=0.2, L1=0.5, W1=0.3, L2=1.0, W2=0.6,
                    col_tol=0.2, s1=2.0):
     """initquadBranchMPC(3,3,N,NB,...) + the main_quadruped.py:15-30 constants

@@ -12,7 +12,7 @@
 
 #include <type_traits>
 
-#include "bmpc_env.h"
+#include "bmpc_env_merge.h"
 #include "bmpc_hmm.h"
 #include "bmpc_plan.h"
 #include "bmpc_qp.h"
@@ -443,14 +443,62 @@ __device__ __attribute__((noinline)) void loop_env_step(const bmpc_env_desc& env
   env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr);
 }
 
-// nsteps closed-loop steps of one ego per wave (bmpc_loop_device): k_env's scene step (lane 0),
-// k_tree's tree step and k_ipm's solve + unpack, in that order, per step -- the same per-ego
-// functions the three launches run, so the same bits -- with no device-wide boundary between
-// the steps: the egos' loops are independent, and a wave whose ego needs few IPM iterations in
-// one step starts its next step instead of idling until the slowest ego of the batch finishes.
-template <class M, bool TL>
+// One merge-scene step of one ego into its slab (k_env_merge and the merge k_loop): the scene
+// function writes S and bx straight into the ego's transform slots and marks them set (S on),
+// which is all bmpc_set_transform would have scattered there.
+__device__ __forceinline__ void merge_env_step_slab(const bmpc_merge_env_desc& env, const MergeRef& R, const Plan& P,
+                                                    const Layout& L, int t, double* st, double* ws, const double* up,
+                                                    double* x, double* z, double* xr) {
+  double* xf = ws + L.xform;
+  merge_env_step_ego(env, R, P.desc.bx, P.nFx, P.desc.dt, t, st, up, x, z, xr, xf + XF_S, xf + XF_BX);
+  xf[XF_SON] = 1.0;
+  xf[XF_BXSET] = 1.0;
+}
+__device__ __attribute__((noinline)) void loop_merge_env_step(const bmpc_merge_env_desc& env, const MergeRef& R,
+                                                              const Plan& P, const Layout& L, int t, double* st,
+                                                              double* ws, const double* up, double* x, double* z,
+                                                              double* xr, double Jv, int status, int iters,
+                                                              double* stats) {
+  if (t > 0 && stats) env_accumulate(st, Jv, status, iters, true, stats);
+  merge_env_step_slab(env, R, P, L, t, st, ws, up, x, z, xr);
+}
+
+#ifndef BMPC_MERGE_LOOP_INLINE_IPM
+#define BMPC_MERGE_LOOP_INLINE_IPM 1
+#endif
+// The scene of a k_loop (its kernel argument): one ego's scene step on lane 0, through an
+// out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
+// ego's transform slots.  kInlineIpm: the IPM inlined into the kernel as k_ipm has it (the tree
+// and scene steps stay calls) instead of a call of its own -- as a callee the IPM's frame grows
+// from k_ipm's ~590 to ~1,490 bytes per lane (merge loop: 2,528 bytes of scratch against 1,648;
+// DESIGN §5c).  The overtake loop keeps the form it was measured in (§5b).
+struct OvertakeScene {
+  static constexpr bool kInlineIpm = false;
+  bmpc_env_desc env;
+  __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
+                       double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
+    loop_env_step(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, Jv, status, iters, stats);
+  }
+};
+struct MergeScene {
+  static constexpr bool kInlineIpm = BMPC_MERGE_LOOP_INLINE_IPM != 0;
+  bmpc_merge_env_desc env;
+  MergeRef ref;
+  __device__ void step(const Plan& P, const Layout& L, int t, double* st, bmpc_policy*, double* ws, const double* up,
+                       double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
+    loop_merge_env_step(env, ref, P, L, t, st, ws, up, x, z, xr, Jv, status, iters, stats);
+  }
+};
+
+// nsteps closed-loop steps of one ego per wave (bmpc_loop_device, bmpc_merge_loop_device): the
+// scene step of k_env / k_env_merge (lane 0), k_tree's tree step and k_ipm's solve + unpack, in
+// that order, per step -- the same per-ego functions the three launches run, so the same bits --
+// with no device-wide boundary between the steps: the egos' loops are independent, and a wave
+// whose ego needs few IPM iterations in one step starts its next step instead of idling until the
+// slowest ego of the batch finishes.
+template <class M, bool TL, class SC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) void k_loop(
-    const Bundle* __restrict__ B, double* __restrict__ ws, bmpc_policy* __restrict__ pol, bmpc_env_desc env, int t0,
+    const Bundle* __restrict__ B, double* __restrict__ ws, bmpc_policy* __restrict__ pol, SC sc, int t0,
     int nsteps, double* scene, double* upred, double* xs, double* zs, double* xrefs, double* J, int32_t* status,
     int32_t* iters, double* stats, int batch) {
   const int e = blockIdx.x;
@@ -469,12 +517,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const int lane = threadIdx.x;
   for (int s = 0; s < nsteps; ++s) {
     const int t = t0 + s;
-    if (lane == 0)   // k_env
-      loop_env_step(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, J[e], status[e], iters[e],
-                    stats ? stats + (size_t)e * ENVS_STRIDE : nullptr);
+    if (lane == 0)   // k_env / k_env_merge
+      sc.step(P, L, t, st, pe, E.ws, up, x, z, xr, J[e], status[e], iters[e],
+              stats ? stats + (size_t)e * ENVS_STRIDE : nullptr);
     __syncthreads();
-    loop_tree_step<DevExecT<M::kTransform, TL>, M>(ex, P, L, E, x, z, xr);   // k_tree
-    const IpmResult r = loop_ipm<DevExecT<M::kTransform, TL>, M>(ex, P, L, E);   // k_ipm
+    using X = DevExecT<M::kTransform, TL>;
+    loop_tree_step<X, M>(ex, P, L, E, x, z, xr);   // k_tree
+    IpmResult r;   // k_ipm
+    if constexpr (SC::kInlineIpm) r = solve_ego_ipm<X, M>(ex, P, L, E);
+    else r = loop_ipm<X, M>(ex, P, L, E);
     const double* w = E.ws;
     for (int i = lane; i < P.U * P.d; i += 64) up[i] = w[L.upred + i];
     if (lane == 0) {
@@ -565,17 +616,16 @@ hipError_t launch_solver(const SolveLaunch& a) {
 }
 
 // the fused closed loop (k_loop): the one-wave IPM's LDS and register budget
-template <class M>
-hipError_t launch_loop(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
-                       double* stats) {
-  void (*k)(const Bundle*, double*, bmpc_policy*, bmpc_env_desc, int, int, double*, double*, double*, double*,
-            double*, double*, int32_t*, int32_t*, double*, int) = a.rich ? k_loop<M, true> : k_loop<M, false>;
+template <class M, class SC>
+hipError_t launch_loop(const SolveLaunch& a, const SC& sc, int t0, int nsteps, double* scene, double* stats) {
+  void (*k)(const Bundle*, double*, bmpc_policy*, SC, int, int, double*, double*, double*, double*, double*, double*,
+            int32_t*, int32_t*, double*, int) = a.rich ? k_loop<M, true, SC> : k_loop<M, false, SC>;
   if (a.lds_bytes > 64 * 1024) {
     const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k, dim3(a.batch), dim3(64), a.lds_bytes, a.stream, a.bundle, a.ws, const_cast<bmpc_policy*>(a.pol),
-                     env, t0, nsteps, scene, a.upred, const_cast<double*>(a.x), const_cast<double*>(a.z),
+                     sc, t0, nsteps, scene, a.upred, const_cast<double*>(a.x), const_cast<double*>(a.z),
                      const_cast<double*>(a.xref), a.J, a.status, a.iters, stats, a.batch);
   return hipGetLastError();
 }
@@ -623,6 +673,9 @@ hipError_t launch_solver_blk_merge(const SolveLaunch& a);
 hipError_t launch_solver_blk_quadruped(const SolveLaunch& a);
 hipError_t launch_loop_highway(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
                                double* stats);
+// (bmpc_k_merge_loop.hip)
+hipError_t launch_loop_merge(const SolveLaunch& a, const bmpc_merge_env_desc& env, const MergeRef& ref, int t0,
+                             int nsteps, double* scene, double* stats);
 #if defined(BMPC_WITH_PHASED)
 // the phase-per-kernel CVaR IPM (experimental/bmpc_kp_*.hip; tools-only builds with -DBMPC_WITH_PHASED)
 hipError_t launch_ipm_phased_highway(const SolveLaunch& a);

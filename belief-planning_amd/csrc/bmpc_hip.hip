@@ -57,6 +57,22 @@ __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, in
                x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4);
 }
 
+// one thread per ego: the merge scene step (bmpc_env_merge.h) around the solve; S, bx and their
+// flags go straight into the ego's transform slots (no bmpc_set_transform before the solve)
+__global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E, MergeRef R, int t, int batch,
+                            double* scene, double* ws, const double* upred, const double* J, const int32_t* status,
+                            const int32_t* iters, double* x, double* z, double* xref, double* stats) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= batch) return;
+  const Plan& P = B->P;
+  const Layout& L = B->L;
+  double* st = scene + (size_t)e * ENV_STRIDE;
+  if (t > 0 && stats && J && status && iters)
+    env_accumulate(st, J[e], status[e], iters[e], true, stats + (size_t)e * ENVS_STRIDE);
+  merge_env_step_slab(E, R, P, L, t, st, ws + L.stride * (size_t)e, upred ? upred + (size_t)e * P.U * P.d : nullptr,
+                      x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4);
+}
+
 __global__ void k_gather(const double* __restrict__ ws, size_t stride, size_t off, int count,
                          double* __restrict__ out, int batch) {
   const size_t tot = (size_t)batch * count;
@@ -272,6 +288,10 @@ struct bmpc_plan {
   Layout* d_blk_lay = nullptr;
   size_t blk_lay_base = 0, blk_hot_off = 0, blk_hot_bytes = 0;
   bool psiref = false;        // some policy in force tracks the lane reference
+  // the merge scene (bmpc_set_merge_scene): its constants and lane references (grid | refY | refpsi)
+  bmpc_merge_env_desc menv = {};
+  double* d_mref = nullptr;
+  int n_mref = 0;   // 0: no merge scene set
 #if defined(BMPC_WITH_PHASED)
   int32_t* d_count = nullptr;   // phase-per-kernel IPM: egos going on per iteration [kMaxSub][maxit + 1]
   int32_t* h_count = nullptr;   // ... pinned read-back slots [kMaxSub]
@@ -388,6 +408,7 @@ int bmpc_plan_destroy(bmpc_plan* pl) {
   hipFree(pl->d_iout);
   hipFree(pl->d_scratch);
   hipFree(pl->d_lref);
+  hipFree(pl->d_mref);
   hipFree(pl->d_blk_lay);
   for (auto& e : pl->ev)
     if (e) hipEventDestroy(e);
@@ -808,6 +829,98 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
   return 0;
 }
 
+int bmpc_set_merge_scene(bmpc_plan* pl, const bmpc_merge_env_desc* desc, int nref, const double* grid,
+                         const double* refY, const double* refpsi) {
+  if (!pl || !desc) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (P.desc.model != BMPC_MODEL_HIGHWAY_MERGE || P.desc.controller != BMPC_CTRL_CVAR || P.n != 4 || P.d != 2 ||
+      P.nFx != 4)
+    return fail(-22, "bmpc_set_merge_scene: the merge scene needs a HIGHWAY_MERGE CVaR plan (n = 4, d = 2, nFx = 4)");
+  if (nref < 2) return fail(-22, "bmpc_set_merge_scene: lane reference: need 2 <= nref <= BMPC_MAX_LANE_REF");
+  for (const double* v : {refY, refpsi}) {
+    const std::string e = check_lane_ref(nref, grid, v);
+    if (!e.empty()) return fail(-22, "bmpc_set_merge_scene: " + e);
+  }
+  if (desc->n_lane < 1 || desc->merge_lane < 1) return fail(-22, "bmpc_set_merge_scene: n_lane, merge_lane >= 1");
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  HIPCHECK(hipStreamSynchronize(pl->stream));   // no scene step in flight reads the old tables
+  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  DevBuf fresh;
+  HIPCHECK(fresh.alloc(sizeof(double) * 3 * (size_t)nref));
+  const double* parts[] = {grid, refY, refpsi};
+  for (int k = 0; k < 3; ++k)
+    HIPCHECK(hipMemcpy(fresh.as<double>() + (size_t)k * nref, parts[k], sizeof(double) * nref, hipMemcpyHostToDevice));
+  hipFree(pl->d_mref);
+  pl->d_mref = fresh.as<double>();
+  fresh.p = nullptr;   // owned by the plan now
+  pl->n_mref = nref;
+  pl->menv = *desc;
+  return 0;
+}
+
+int bmpc_merge_env_step(bmpc_plan* pl, int t, double* d_scene, const double* d_upred, const double* d_J,
+                        const int32_t* d_status, const int32_t* d_iters, double* d_x, double* d_z, double* d_xref,
+                        double* d_stats, void* stream) {
+  if (!pl || !d_scene || !d_x || !d_z || !d_xref) return fail(-22, "null argument");
+  if (!pl->n_mref) return fail(-22, "bmpc_merge_env_step: no merge scene (bmpc_set_merge_scene)");
+  if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_merge_env_step: t > 0 needs the last uPred");
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+  if (stream) pl->user_stream = s;
+  hipLaunchKernelGGL(k_env_merge, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, pl->menv,
+                     MergeRef{pl->d_mref, pl->n_mref}, t, pl->batch, d_scene, pl->d_ws, d_upred, d_J, d_status, d_iters,
+                     d_x, d_z, d_xref, d_stats);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// nsteps closed-loop merge steps (include/bmpc.h): bmpc_loop_device's launch rule and bookkeeping
+int bmpc_merge_loop_device(bmpc_plan* pl, int t0, int nsteps, double* d_scene, double* d_upred, double* d_x,
+                           double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
+                           double* d_stats, void* stream) {
+  if (!pl || !d_scene || !d_upred || !d_x || !d_z || !d_xref || !d_J || !d_status || !d_iters)
+    return fail(-22, "null argument");
+  if (!pl->n_mref) return fail(-22, "bmpc_merge_loop_device: no merge scene (bmpc_set_merge_scene)");
+  if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_merge_loop_device: nsteps >= 1 and t0 >= 0");
+  const Plan& P = pl->hp.plan;
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
+  if (stream) pl->user_stream = s;
+  const int B = pl->batch;
+  int blk_max = pl->ctx->cus;   // the small-batch path of launch_solve
+  if (const char* e = getenv("BMPC_BLOCK_EGOS")) blk_max = atoi(e);
+  bool fused = B > blk_max && !pl->psiref;   // (a merge scene's plan is a CVaR plan)
+  if (const char* e = getenv("BMPC_LOOP_FUSED")) fused = fused && atoi(e) != 0;   // 0: per-step launches (A/B)
+  if (!fused) {
+    for (int k = 0; k < nsteps; ++k) {
+      if (int rc = bmpc_merge_env_step(pl, t0 + k, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats,
+                                       stream))
+        return rc;
+      if (int rc = launch_solve(pl, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters, s)) return rc;
+    }
+    return 0;
+  }
+  if (pl->timing && (pl->t_pending < 0 || pl->t_pending >= bmpc_plan::kTimeSlots))
+    return fail(-5, "timing ring out of range (t_pending = " + std::to_string(pl->t_pending) + ")");
+  const bool tl = choose_lds_rich(P, true, B, pl->ctx->cus, pl->ctx->lds_per_cu);
+  SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status,
+                d_iters, B, solver_lds_bytes(P, true, tl), tl, false, s};
+  a.cus = pl->ctx->cus;
+  a.hplan = &P;
+  pl->last_kernel = tl ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
+  hipEvent_t* ev = pl->ev + 3 * (pl->timing ? pl->t_pending : 0);
+  if (pl->timing) {   // (the whole fused launch is booked as the solver's time, none as the tree's)
+    HIPCHECK(hipEventRecord(ev[0], s));
+    HIPCHECK(hipEventRecord(ev[1], s));
+  }
+  HIPCHECK(launch_loop_merge(a, pl->menv, MergeRef{pl->d_mref, pl->n_mref}, t0, nsteps, d_scene, d_stats));
+  if (pl->timing) {
+    HIPCHECK(hipEventRecord(ev[2], s));
+    if (++pl->t_pending == bmpc_plan::kTimeSlots) return fold_timing(pl);
+  }
+  return 0;
+}
+
 static int gather(bmpc_plan* pl, size_t off, int count, double* host) {
   if (!host) return 0;
   const size_t need = (size_t)pl->batch * count;
@@ -943,6 +1056,20 @@ int bmpc_set_fx(bmpc_plan* pl, const double* Fx, const uint8_t* mask) {
   std::vector<double> ones(B, 1.0);
   if (int rc = scatter_rows(pl, Fx, L.xform + XF_FX, P.nFx * P.n, dmask.as<uint8_t>())) return rc;
   return scatter_rows(pl, ones.data(), L.xform + XF_FXSET, 1, dmask.as<uint8_t>());
+}
+
+int bmpc_get_transform(bmpc_plan* pl, double* S, double* bx, double* flags) {
+  if (!pl) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (!plan_takes_transform(P)) return fail(-22, "bmpc_get_transform: the plan takes no state transformation");
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  const Layout& L = pl->hp.lay;
+  int rc;
+  if ((rc = gather(pl, L.xform + XF_S, P.n * P.n, S))) return rc;
+  if ((rc = gather(pl, L.xform + XF_BX, P.nFx, bx))) return rc;
+  static_assert(XF_BXSET == XF_SON + 1, "the two flags are gathered as one pair");
+  return gather(pl, L.xform + XF_SON, 2, flags);
 }
 
 int bmpc_get_branch_dp(bmpc_plan* pl, double* dp) {

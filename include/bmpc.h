@@ -29,6 +29,8 @@
  *                         the psiref backups              main_branch.py:78-85
  *   bmpc_env_step      <- Highway_env.step + Highway_sim collision rule
  *                                                          Highway_env_branch.py:83-184,421-429
+ *   bmpc_merge_env_step<- Highway_env_merge.step + the same collision rule
+ *                                                          Highway_env_branch.py:317-380,421-429
  *
  * Conventions: all host buffers are caller-owned, C-contiguous, ego-major, float64
  * (int32 for status/iteration counts).  Return codes are 0 on success and a negative
@@ -251,6 +253,10 @@ int bmpc_set_transform(bmpc_plan* plan, const double* S, const uint8_t* s_on, co
  * enters the state rows under the rule of bmpc_set_transform (first solve, or S on).  Same
  * plans as bmpc_set_transform; the row count must stay nFx.  mask NULL = all egos. */
 int bmpc_set_fx(bmpc_plan* plan, const double* Fx, const uint8_t* mask);
+/* The transform in force (host copies; NULL skips): S [batch][n][n], bx [batch][nFx] and
+ * flags [batch][2] = {S is on, bx was set} -- what bmpc_set_transform or the device merge scene
+ * (bmpc_merge_env_step) last wrote.  Same plans as bmpc_set_transform. */
+int bmpc_get_transform(bmpc_plan* plan, double* S, double* bx, double* flags);
 
 /* Tree of the last solve (host copies; NULL skips):
  *   xbar,zbar [batch][T][n]  ubar [batch][U][d]  w [batch][nbranch]
@@ -343,6 +349,44 @@ int bmpc_env_step(bmpc_plan* plan, const bmpc_env_desc* env, int t, double* d_sc
 int bmpc_loop_device(bmpc_plan* plan, const bmpc_env_desc* env, int t0, int nsteps, double* d_scene,
                      double* d_upred, double* d_x, double* d_z, double* d_xref, double* d_J,
                      int32_t* d_status, int32_t* d_iters, double* d_stats, void* stream);
+
+/* Closed-loop sim_merge scene on the device, one scene per ego of a HIGHWAY_MERGE plan: replaces
+ * Highway_env_branch.Highway_env_merge.step (Highway_env_branch.py:317-380) around the solve and
+ * the collision rule of Highway_sim (:421-429).  The ego starts on the ramp, the obstacle on the
+ * main road and keeps backup 0 of the main-road list (maintain_trackV(v0), :345-347). */
+typedef struct {
+  int32_t n_lane;      /* lanes of the main road (x_ref after the merge: (n_lane - 0.5) 3.6)  */
+  int32_t merge_lane;  /* lanes the ramp spans (the ramp's upper bound, :361)                  */
+  double merge_s;      /* a vehicle with X > merge_s + 8 has left the ramp (:328-329)         */
+  double W, Kpsi;      /* Branch_constants                                                   */
+  double v0;           /* 20 (Highway_env_branch.py:19)                                       */
+  double psimax;       /* BranchMPC_CVaR.psimax (0.25): the ramp's heading bound around psi0  */
+  double vlen, vwid;   /* vehicle() size 4 x 2.4 (:29), used by the collision test            */
+} bmpc_merge_env_desc;
+
+/* The merge scene of a plan: its constants and the ramp's lane references refY(X), refpsi(X),
+ * linear interpolants of refY [nref] / refpsi [nref] over one increasing grid [nref]
+ * (2 <= nref <= BMPC_MAX_LANE_REF; :308-309), copied to the device and kept with the plan.
+ * HIGHWAY_MERGE CVaR plans with n = 4, d = 2 and nFx = 4; -22 otherwise.  Independent of
+ * bmpc_set_lane_ref: the scene's controller uses the main-road model (no psiref policies). */
+int bmpc_set_merge_scene(bmpc_plan* plan, const bmpc_merge_env_desc* desc, int nref, const double* grid,
+                         const double* refY, const double* refpsi);
+
+/* One closed-loop merge step t of every ego: bmpc_env_step's arguments without the env (the
+ * plan's merge scene; -22 when none was set).  scene [batch][BMPC_ENV_STRIDE]: ego x[0..3],
+ * obstacle z[4..7], slot 10 = "the ego has merged" (0 on the ramp), the rest as bmpc_env_step's;
+ * all zero but x, z at t = 0.  Besides x, z and xref it writes the solve's S (on), and bx into
+ * the egos' transform slots: the next bmpc_solve_device needs no bmpc_set_transform. */
+int bmpc_merge_env_step(bmpc_plan* plan, int t, double* d_scene, const double* d_upred, const double* d_J,
+                        const int32_t* d_status, const int32_t* d_iters, double* d_x, double* d_z,
+                        double* d_xref, double* d_stats, void* stream);
+
+/* nsteps closed-loop merge steps: bmpc_loop_device's arguments without the env, the same
+ * contract (bmpc_merge_env_step(t) then bmpc_solve_device per step, bit for bit; ONE k_loop
+ * launch when the batch takes the one-wave IPM, BMPC_KERNEL_LOOP_RICH / _LEAN). */
+int bmpc_merge_loop_device(bmpc_plan* plan, int t0, int nsteps, double* d_scene, double* d_upred,
+                           double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status,
+                           int32_t* d_iters, double* d_stats, void* stream);
 
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of
