@@ -212,6 +212,7 @@ struct Layout {
   // IPM vectors
   size_t x, y, z, s, lam, x1, y1, z1, x2, y2, z2, dz, ds, rx, ry, rz, hvec, bvec;
   size_t ta, ta2, ya, ra, rb, rc, bestx;
+  size_t ej;     // -e_J, the c direction's right-hand side (written once per solve)
   // ECOS's equilibration of this solve (bmpc_ipm.h equilibrate): column factors (nv), A row factors
   // (neq), G row factors (nrows; one value per second-order cone)
   size_t xeq, aeq, geq;

@@ -58,6 +58,11 @@
 #ifndef BMPC_FLAT_PAIR
 #define BMPC_FLAT_PAIR 1     // 1: the IPM loop calls the pair's coupling solve and refinement directly
 #endif
+#ifndef BMPC_IPM_LEAN_PASSES
+#define BMPC_IPM_LEAN_PASSES 1  // 1: the IPM iteration without the passes and re-reads its result does not need (same
+                                // values from the same expressions; 0: the separate passes, kept for the A/B and
+                                // tests/test_ipm_lean_passes.py)
+#endif
 #ifndef BMPC_PAIR_BACK
 #define BMPC_PAIR_BACK 1     // kkt_solve_pair's two back halves in one pass over the Woodbury data
 #endif
@@ -1132,17 +1137,33 @@ BMPC_FN_MAX_STEP double max_step(const X ex, const Ctx Cin, const gdouble* lam, 
   return ex.max(bad) > 0.0 ? 0.0 : a;
 }
 
-// both step lengths of an IPM step in one pass over lam: min(max_step(lam, d1), max_step(lam, d2))
+// this lane's minima of the step-length ratios -lam / min(d, -0) over its LP rows, for two directions
+struct LpSteps { double a1, a2; };
 template <class X>
-BMPC_FN_MAX_STEP double max_step2(const X ex, const Ctx Cin, const gdouble* lam, const gdouble* d1, const gdouble* d2) {
-  const Ctx C = Cin.uniform();
-  CPlan& P = *C.P;
+BMPC_HD LpSteps lp_steps(const X& ex, CPlan& P, const gdouble* lam, const gdouble* d1, const gdouble* d2) {
   struct A2 { double a, b; };
-  double a1 = 1e300, a2 = 1e300;
+  LpSteps m{1e300, 1e300};
   lane_batch<8>(ex, 0, P.nlp, [&](int i) {
     const double l = lam[i], u = d1[i], v = d2[i];
     return A2{-l / fmin(u, -0.0), -l / fmin(v, -0.0)};   // +inf where the direction is >= 0
-  }, [&](int, A2 r) { a1 = fmin(a1, r.a); a2 = fmin(a2, r.b); });
+  }, [&](int, A2 r) { m.a1 = fmin(m.a1, r.a); m.a2 = fmin(m.a2, r.b); });
+  return m;
+}
+
+// both step lengths of an IPM step in one pass over lam: min(max_step(lam, d1), max_step(lam, d2)).
+// With HAVE_LP the LP rows' minima come from the pass that formed d1 and d2 (affine_dirs /
+// combined_dirs held those rows in registers): a minimum is exact, so where it is taken does
+// not change it.
+template <class X, bool HAVE_LP = false>
+BMPC_FN_MAX_STEP double max_step2(const X ex, const Ctx Cin, const gdouble* lam, const gdouble* d1, const gdouble* d2,
+                                  double lp1 = 1e300, double lp2 = 1e300) {
+  const Ctx C = Cin.uniform();
+  CPlan& P = *C.P;
+  double a1 = lp1, a2 = lp2;
+  if (!HAVE_LP) {
+    const LpSteps m = lp_steps(ex, P, lam, d1, d2);
+    a1 = m.a1, a2 = m.a2;
+  }
   double bad = 0.0;
   BMPC_CONE_ROUNDS(ex, P, G) {
     BMPC_CONE_K(P, G, k, off, q);
@@ -1222,13 +1243,16 @@ BMPC_FN_FUSED void apply_Winv2(const X ex, const Ctx Cin, const gdouble* in, gdo
   ex.sync();
 }
 
-// the affine step's directions in one pass: dz = z2 + t z1, rb = W dz, ds = -lam - rb
+// the affine step's directions in one pass: dz = z2 + t z1, rb = W dz, ds = -lam - rb.  Returns
+// this lane's LP-row minima of max_step2(lam, ds, rb) (BMPC_IPM_LEAN_PASSES), taken as each row is
+// formed; a batch's clamped slots repeat an element of the lane, which a minimum ignores.
 template <class X>
-BMPC_FN_FUSED void affine_dirs(const X ex, const Ctx Cin, const gdouble* z2, const gdouble* z1, double t,
-                               const gdouble* lam, gdouble* rb, gdouble* ds) {
+BMPC_FN_FUSED LpSteps affine_dirs(const X ex, const Ctx Cin, const gdouble* z2, const gdouble* z1, double t,
+                                  const gdouble* lam, gdouble* rb, gdouble* ds) {
   const Ctx C = Cin.uniform();
   z2 = uniform_ptr(z2), z1 = uniform_ptr(z1), lam = uniform_ptr(lam), rb = uniform_ptr(rb), ds = uniform_ptr(ds);
   CPlan& P = *C.P;
+  LpSteps m{1e300, 1e300};
   if (!cone_regs(ex, P)) {
     gdouble* dz = C.at(C.L->dz);
     lane_batch<8>(ex, 0, P.nrows, [&](int i) { return z2[i] + t * z1[i]; }, [&](int i, double v) { dz[i] = v; });
@@ -1236,7 +1260,7 @@ BMPC_FN_FUSED void affine_dirs(const X ex, const Ctx Cin, const gdouble* z2, con
     apply_W(ex, C, 0, dz, rb);
     lane_batch<8>(ex, 0, P.nrows, [&](int i) { return -lam[i] - rb[i]; }, [&](int i, double v) { ds[i] = v; });
     ex.sync();
-    return;
+    return BMPC_IPM_LEAN_PASSES ? lp_steps(ex, P, lam, ds, rb) : m;
   }
   BMPC_PROF(C.ws, *C.L, PROF_APPLYW);
   constexpr int UC = X::kConeRegRows;
@@ -1244,7 +1268,14 @@ BMPC_FN_FUSED void affine_dirs(const X ex, const Ctx Cin, const gdouble* z2, con
   struct Two { double a, b; };
   lane_batch<8>(ex, 0, P.nlp, [&](int i) {
     const double r = dl[i] * (z2[i] + t * z1[i]);
+#if BMPC_IPM_LEAN_PASSES
+    const double l = lam[i], d = -l - r;
+    m.a1 = fmin(m.a1, -l / fmin(d, -0.0));
+    m.a2 = fmin(m.a2, -l / fmin(r, -0.0));
+    return Two{r, d};
+#else
     return Two{r, -lam[i] - r};
+#endif
   }, [&](int i, Two v) { rb[i] = v.a; ds[i] = v.b; });
   const gdouble* vn = C.at(C.L->vnt);
   const gdouble* eta = C.at(C.L->eta);
@@ -1273,16 +1304,19 @@ BMPC_FN_FUSED void affine_dirs(const X ex, const Ctx Cin, const gdouble* z2, con
     }
   }
   ex.sync();
+  return m;
 }
 
 // the combined step's directions in one pass: z2 += t z1 (dz), rb = W dz, ds -= rb (dsW) and
-// rc = W dsW (the s update)
+// rc = W dsW (the s update).  Returns this lane's LP-row minima of max_step2(lam, ds, rb), as
+// affine_dirs does.
 template <class X>
-BMPC_FN_FUSED void combined_dirs(const X ex, const Ctx Cin, gdouble* z2, const gdouble* z1, double t, gdouble* ds,
-                                 gdouble* rb, gdouble* rc) {
+BMPC_FN_FUSED LpSteps combined_dirs(const X ex, const Ctx Cin, gdouble* z2, const gdouble* z1, double t, gdouble* ds,
+                                    gdouble* rb, gdouble* rc) {
   const Ctx C = Cin.uniform();
   z2 = uniform_ptr(z2), z1 = uniform_ptr(z1), ds = uniform_ptr(ds), rb = uniform_ptr(rb), rc = uniform_ptr(rc);
   CPlan& P = *C.P;
+  LpSteps m{1e300, 1e300};
   if (!cone_regs(ex, P)) {
     lane_batch<8>(ex, 0, P.nrows, [&](int i) { return z2[i] + t * z1[i]; }, [&](int i, double v) { z2[i] = v; });
     ex.sync();
@@ -1290,17 +1324,25 @@ BMPC_FN_FUSED void combined_dirs(const X ex, const Ctx Cin, gdouble* z2, const g
     lane_batch<8>(ex, 0, P.nrows, [&](int i) { return ds[i] - rb[i]; }, [&](int i, double v) { ds[i] = v; });
     ex.sync();
     apply_W(ex, C, 0, ds, rc);
-    return;
+    return BMPC_IPM_LEAN_PASSES ? lp_steps(ex, P, C.at(C.L->lam), ds, rb) : m;
   }
   BMPC_PROF(C.ws, *C.L, PROF_APPLYW);
   constexpr int UC = X::kConeRegRows;
   const gdouble* dl = C.at(C.L->dl);
+#if BMPC_IPM_LEAN_PASSES
+  const gdouble* lam = C.at(C.L->lam);
+#endif
   struct Four { double z, r, d, c; };
   lane_batch<4>(ex, 0, P.nlp, [&](int i) {
     const double w = dl[i];
     const double z = z2[i] + t * z1[i];
     const double r = w * z;
     const double d = ds[i] - r;
+#if BMPC_IPM_LEAN_PASSES
+    const double l = lam[i];
+    m.a1 = fmin(m.a1, -l / fmin(d, -0.0));
+    m.a2 = fmin(m.a2, -l / fmin(r, -0.0));
+#endif
     return Four{z, r, d, w * d};
   }, [&](int i, Four v) { z2[i] = v.z; rb[i] = v.r; ds[i] = v.d; rc[i] = v.c; });
   const gdouble* vn = C.at(C.L->vnt);
@@ -1338,6 +1380,7 @@ BMPC_FN_FUSED void combined_dirs(const X ex, const Ctx Cin, gdouble* z2, const g
     }
   }
   ex.sync();
+  return m;
 }
 
 // the combined step's right-hand side in one pass (ECOS, oracle/ecos_ipm.py): with
@@ -3464,6 +3507,38 @@ BMPC_HD double dot2(const X ex, const gdouble* a1, const gdouble* b1, int n1, co
   });
 }
 
+#if BMPC_IPM_LEAN_PASSES
+// dot2(a1, b1, n1, a2, b2, n2) and dot2(a1, c1, n1, a2, c2, n2) in one pass: a1 and a2 are loaded
+// once; each sum keeps dot2's accumulators, index-to-lane mapping and reduction
+template <class X>
+BMPC_HD void dot2_pair(const X ex, const gdouble* a1, const gdouble* b1, const gdouble* c1, int n1, const gdouble* a2,
+                       const gdouble* b2, const gdouble* c2, int n2, double& sb, double& sc) {
+  constexpr int UN = Narrow<8, X>::v;
+  const int hi = n1 + n2, stride = ex.nlanes;
+  double accb[UN], accc[UN];
+#pragma unroll
+  for (int u = 0; u < UN; ++u) accb[u] = accc[u] = 0.0;
+  for (int b = ex.lane; b < hi; b += UN * stride) {
+#pragma unroll
+    for (int u = 0; u < UN; ++u) {
+      const int i = b + u * stride;
+      const bool in = i < hi;
+      const int ic = in ? i : b;
+      const bool f = ic < n1;
+      const int j = f ? ic : ic - n1;
+      const double a = (f ? a1 : a2)[j], m = in ? 1.0 : 0.0;
+      accb[u] += m * (a * (f ? b1 : b2)[j]);
+      accc[u] += m * (a * (f ? c1 : c2)[j]);
+    }
+  }
+  double s[2] = {0.0, 0.0};
+#pragma unroll
+  for (int u = 0; u < UN; ++u) s[0] = s[0] + accb[u], s[1] = s[1] + accc[u];
+  ex.template sum_n<2>(s);
+  sb = s[0], sc = s[1];
+}
+#endif
+
 // ------------------------------------------------------------------------------------
 // ECOS's equilibration (ECOS_setup -> set_equilibration, ECOS 2.0.x equil.c with RUIZ_EQUIL and
 // EQUIL_ITERS = 3; restated in oracle/ecos_ipm.py:equilibration).  ECOS runs its IPM on
@@ -3733,11 +3808,13 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
     lane_batch<16>(ex, 0, nr, [&](int i) { return gq[i] * s[i]; }, [&](int i, double v) { s[i] = v; });
     ex.sync();
   }
-  lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { tA[i] = v; });
+  // -c = -e_J: this solve's right-hand side and the c direction's of every iteration
+  gdouble* ej = BMPC_IPM_LEAN_PASSES ? ws + L.ej : tA;
+  lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { ej[i] = v; });
   lane_batch(ex, 0, neq, [&](int i) { return 0.0; }, [&](int i, double v) { ya[i] = v; });
   lane_batch<16>(ex, 0, nr, [&](int i) { return 0.0; }, [&](int i, double v) { ra[i] = v; });
   ex.sync();
-  kkt_solve<X, NX, NU>(ex, C, tA, ya, ra, x2, y, z2, BMPC_NITREF_INIT);
+  kkt_solve<X, NX, NU>(ex, C, ej, ya, ra, x2, y, z2, BMPC_NITREF_INIT);
   // z = bring2cone(ge z) / ge
   if (BMPC_EQUIL) {
     lane_batch<16>(ex, 0, nr, [&](int i) { return gq[i] * z2[i]; }, [&](int i, double v) { z2[i] = v; });
@@ -3786,7 +3863,12 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
       const double xi = x[i], q = BMPC_EQUIL ? xq[i] : 1.0;
       const double v = rx[i] + (tA[i] + (i == P.oJ ? tau : 0.0));
       return R2b{v, v / q, q * xi};
-    }, [&](int i, R2b r) { rx[i] = r.v; acx[0] += r.rs * r.rs; acx[1] += r.xs * r.xs; });
+    }, [&](int i, R2b r) {
+      rx[i] = r.v;
+      if (BMPC_IPM_LEAN_PASSES) tA2[i] = -r.v;   // the affine direction's right-hand side, formed with rx
+      acx[0] += r.rs * r.rs;
+      acx[1] += r.xs * r.xs;
+    });
     apply_A<X, NX, NU>(ex, C, x, ry);
     struct R4 { double v, rs, a, ys; };
     lane_batch<8>(ex, 0, neq, [&](int i) {
@@ -3898,35 +3980,43 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
       // right-hand sides of the c direction (-c, bvec, hvec) and the affine direction
       // (-rx, ry, rb = rz - W xi = rz + W lam for xi = -lam), solved together with the
       // Woodbury columns (kkt_solve_pair)
-      lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { tA[i] = v; });
+#if !BMPC_IPM_LEAN_PASSES   // else ej holds -e_J since the initial point, and the residual pass formed tA2 = -rx
+      lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { ej[i] = v; });
       lane_batch<16>(ex, 0, nv, [&](int i) { return -rx[i]; }, [&](int i, double v) { tA2[i] = v; });
+#endif
       apply_W(ex, C, 0, lam, rb, 1.0, rz, 1.0);
 #if BMPC_FLAT_PAIR
-      kkt_pair_rhs<X, NX, NU>(ex, C, tA, tA2, rb);
+      kkt_pair_rhs<X, NX, NU>(ex, C, ej, tA2, rb);
       ok = ex.uniform(kkt_coupling<X, NX, NU>(ex, C, 2));
       if (ok) {
         kkt_pair_back<X, NX, NU>(ex, C, nref == 0);
         if (nref > 0) {
 #if BMPC_PAIR_REFINE
-          kkt_refine_pair<X, NX, NU>(ex, C, tA, bv, ws + L.k_t3, x1, y1, z1, tA2, ry, ws + L.k_t3b, x2, y2, z2, nref);
+          kkt_refine_pair<X, NX, NU>(ex, C, ej, bv, ws + L.k_t3, x1, y1, z1, tA2, ry, ws + L.k_t3b, x2, y2, z2, nref);
 #else
-          kkt_refine<X, NX, NU>(ex, C, tA, bv, ws + L.k_t3, x1, y1, z1, nref);
+          kkt_refine<X, NX, NU>(ex, C, ej, bv, ws + L.k_t3, x1, y1, z1, nref);
           kkt_refine<X, NX, NU>(ex, C, tA2, ry, ws + L.k_t3b, x2, y2, z2, nref);
 #endif
         }
       }
 #else
-      ok = ex.uniform(kkt_solve_pair<X, NX, NU>(ex, C, tA, tA2, rb, nref));
+      ok = ex.uniform(kkt_solve_pair<X, NX, NU>(ex, C, ej, tA2, rb, nref));
 #endif
     }
     if (ok) {
-      const double den = kap / tau - (x1[P.oJ] + dot2(ex, bv, y1, neq, hv, z1, nr));
+#if BMPC_IPM_LEAN_PASSES
+      double by1, by2;   // bv'y1 + hv'z1 and bv'y2 + hv'z2 in one pass over bv and hv
+      dot2_pair(ex, bv, y1, y2, neq, hv, z1, z2, nr, by1, by2);
+#else
+      const double by1 = dot2(ex, bv, y1, neq, hv, z1, nr), by2 = dot2(ex, bv, y2, neq, hv, z2, nr);
+#endif
+      const double den = kap / tau - (x1[P.oJ] + by1);
       const double dk_aff = -kap * tau;
-      const double dtau_a = (rt + dk_aff / tau + x2[P.oJ] + dot2(ex, bv, y2, neq, hv, z2, nr)) / den;
+      const double dtau_a = (rt + dk_aff / tau + x2[P.oJ] + by2) / den;
       // dz_aff = z2 + dtau_a z1, rb = W dz_aff, ds = dsW_aff = xi - W dz_aff (one pass)
-      affine_dirs(ex, C, z2, z1, dtau_a, lam, rb, ds);
+      const LpSteps lpa = affine_dirs(ex, C, z2, z1, dtau_a, lam, rb, ds);
       const double dkap_a = (dk_aff - kap * dtau_a) / tau;
-      double a_aff = max_step2(ex, C, lam, ds, rb);
+      double a_aff = max_step2<X, BMPC_IPM_LEAN_PASSES != 0>(ex, C, lam, ds, rb, lpa.a1, lpa.a2);
       if (dtau_a < 0.0) a_aff = fmin(a_aff, -tau / dtau_a);
       if (dkap_a < 0.0) a_aff = fmin(a_aff, -kap / dkap_a);
       a_aff = fmax(0.0, fmin(a_aff, 0.999));
@@ -3943,27 +4033,49 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
       const double dk_c = -kap * tau - dtau_a * dkap_a + sigma * mu;
       dtau = (eta1 * rt + dk_c / tau + x2[P.oJ] + dot2(ex, bv, y2, neq, hv, z2, nr)) / den;
       double nonfinite = 0.0;   // the step's finiteness check, taken in the pass that forms dx
+#if !BMPC_IPM_LEAN_PASSES
       lane_batch<8>(ex, 0, nv, [&](int i) { return x2[i] + (dtau * x1[i]); }, [&](int i, double v) {
         x2[i] = v;
         if (!isfinite(v)) nonfinite = 1.0;
       });
       lane_batch(ex, 0, neq, [&](int i) { return y2[i] + (dtau * y1[i]); }, [&](int i, double v) { y2[i] = v; });
       ex.sync();
+#endif
       // dz = z2 + dtau z1, rb = W dz, ds = dsW = xi - W dz, rc = W dsW = ds (one pass)
-      combined_dirs(ex, C, z2, z1, dtau, ds, rb, rc);
+      const LpSteps lpc = combined_dirs(ex, C, z2, z1, dtau, ds, rb, rc);
       dkap = (dk_c - kap * dtau) / tau;
-      double a = max_step2(ex, C, lam, ds, rb);
+      double a = max_step2<X, BMPC_IPM_LEAN_PASSES != 0>(ex, C, lam, ds, rb, lpc.a1, lpc.a2);
       if (dtau < 0.0) a = fmin(a, -tau / dtau);
       if (dkap < 0.0) a = fmin(a, -kap / dkap);
       a = fmin(a, 0.999);
       alpha = a * 0.99;           // never step onto or past the cone / tau / kappa boundary
+#if BMPC_IPM_LEAN_PASSES
+      // dx = x2 + dtau x1 and dy = y2 + dtau y1 are formed in the update's own passes (nothing
+      // else reads them; alpha does not depend on them).  A non-finite dx is seen after x was
+      // written: the backtrack below then leaves through the best iterate and x is dead.
+      ok = ex.uniform(isfinite(dtau) && alpha > 1e-10);
+      if (ok) {
+        lane_batch<8>(ex, 0, nv, [&](int i) {
+          const double v = x2[i] + (dtau * x1[i]);
+          if (!isfinite(v)) nonfinite = 1.0;   // (a batch's clamped slots repeat an element of the lane)
+          return x[i] + (alpha * v);
+        }, [&](int i, double v) { x[i] = v; });
+        ok = ex.uniform(ex.max(nonfinite) == 0.0);
+      }
+#else
       const double fin = ex.max(nonfinite);
       ok = ex.uniform(fin == 0.0 && isfinite(dtau) && alpha > 1e-10);
+#endif
       BMPC_TRACE("   step den %.16e dtau_a %.16e a_aff %.16e sigma %.16e dtau %.16e alpha %.16e nref %d ok %d\n",
                  den, dtau_a, a_aff, sigma, dtau, alpha, nref, (int)ok);
       if (ok) {
+#if BMPC_IPM_LEAN_PASSES
+        lane_batch(ex, 0, neq, [&](int i) { return y[i] + (alpha * (y2[i] + (dtau * y1[i]))); },
+                   [&](int i, double v) { y[i] = v; });
+#else
         lane_batch<8>(ex, 0, nv, [&](int i) { return x[i] + (alpha * x2[i]); }, [&](int i, double v) { x[i] = v; });
         lane_batch(ex, 0, neq, [&](int i) { return y[i] + (alpha * y2[i]); }, [&](int i, double v) { y[i] = v; });
+#endif
         struct ZS { double z, s; };
         lane_batch<4>(ex, 0, nr, [&](int i) { return ZS{z[i] + alpha * z2[i], s[i] + alpha * rc[i]}; },
                    [&](int i, ZS v) { z[i] = v.z; s[i] = v.s; });

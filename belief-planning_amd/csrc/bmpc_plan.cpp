@@ -414,6 +414,7 @@ std::string build_plan(const bmpc_plan_desc& desc, HostPlan& hp) {
   L.rb = take(nr);
   L.rc = take(nr);
   L.bestx = take(nv);
+  L.ej = take(nv);
   L.xeq = take(nv);
   L.aeq = take(neq);
   L.geq = take(nr);
