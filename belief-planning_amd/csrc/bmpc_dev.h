@@ -182,18 +182,11 @@ struct DevBlockExecT {
   __device__ void min_n(double* v) const { reduce<2, K>(v); }
 };
 
-#if defined(BMPC_WITH_PHASED)
-constexpr int kMaxSub = 8;   // sub-batch streams of the phase-per-kernel IPM (experimental/)
-#endif
-
 struct Bundle {
   Plan P;
   Layout L;
 };
 
-// Dynamic LDS of the solver kernels: Plan::nlds doubles of scratch, then a copy of the
-// topology tables (Plan::ntab int32).  The copy is one batched pass at kernel start; every
-// later tree / cone / node-index lookup of the solve is an LDS read.
 // Dynamic LDS of the solver kernels: Plan::nlds doubles of scratch, then a copy of the
 // topology tables (Plan::ntab int32), then (transform-capable models) ECO_COUNT doubles of
 // per-ego constants.  The table copy is one batched pass at kernel start; every later tree /
@@ -244,6 +237,27 @@ __device__ __forceinline__ DevBlockExecT<TR, true, NW> solver_exec_blk(const Pla
   if (t < NW) red[2 * 16 * NW + t] = 0.0;   // each wave's reduction turn (BMPC_BLK_RED2)
   __syncthreads();
   return DevBlockExecT<TR, true, NW>{t, (ldouble*)lds_dyn, (lint*)tabl, (ldouble*)eco, (ldouble*)red};
+}
+
+// The solver kernels' epilogue: ego e's predictions out of its slab w (strided over the NT
+// lanes of the workgroup), then the cost (*Jsrc: the IPM's slot of the solution, or the QP's
+// primal cost), the exit code and the iteration count on lane 0.  Null outputs are skipped.
+template <int NT>
+__device__ __forceinline__ void write_outputs(const Plan& P, const Layout& L, const double* w, int e,
+                                              const double* Jsrc, const IpmResult& r, double* upred, double* xpred,
+                                              double* bw, double* J, int32_t* status, int32_t* iters) {
+  const int lane = threadIdx.x;
+  if (upred)
+    for (int i = lane; i < P.U * P.d; i += NT) upred[(size_t)e * P.U * P.d + i] = w[L.upred + i];
+  if (xpred)
+    for (int i = lane; i < P.T * P.n; i += NT) xpred[(size_t)e * P.T * P.n + i] = w[L.xpred + i];
+  if (bw)
+    for (int i = lane; i < P.nbranch - 1; i += NT) bw[(size_t)e * (P.nbranch - 1) + i] = w[L.w + 1 + i];
+  if (lane == 0) {
+    if (J) J[e] = *Jsrc;
+    if (status) status[e] = r.exit_flag;
+    if (iters) iters[e] = r.iters;
+  }
 }
 
 // One ego per workgroup of NW waves (small batches: every wave of the chip on few egos);
@@ -301,18 +315,7 @@ __global__ __launch_bounds__(64 * NW) void k_solve_blk(const Bundle* __restrict_
   if constexpr (QP) r = solve_ego_qp<X, M>(ex, P, L, E);
   else r = solve_ego_ipm<X, M>(ex, P, L, E);
   const double* w = E.ws;
-  const int lane = threadIdx.x, nt = 64 * NW;
-  if (upred)
-    for (int i = lane; i < P.U * P.d; i += nt) upred[(size_t)e * P.U * P.d + i] = w[L.upred + i];
-  if (xpred)
-    for (int i = lane; i < P.T * P.n; i += nt) xpred[(size_t)e * P.T * P.n + i] = w[L.xpred + i];
-  if (bw)
-    for (int i = lane; i < P.nbranch - 1; i += nt) bw[(size_t)e * (P.nbranch - 1) + i] = w[L.w + 1 + i];
-  if (lane == 0) {
-    if (J) J[e] = QP ? r.pcost : w[L.sol + P.oJ];
-    if (status) status[e] = r.exit_flag;
-    if (iters) iters[e] = r.iters;
-  }
+  write_outputs<64 * NW>(P, L, w, e, QP ? &r.pcost : w + L.sol + P.oJ, r, upred, xpred, bw, J, status, iters);
 }
 
 #if defined(BMPC_BLK2)
@@ -331,19 +334,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(BMPC_WPE)))
   const auto ex = solver_exec_blk<M::kTransform, 2>(P, lds_dyn);
   EgoView E{ws + L.stride * (size_t)e, pol + (size_t)e * P.m};
   IpmResult r = solve_ego_ipm<DevBlockExecT<M::kTransform, true, 2>, M>(ex, P, L, E);
-  const double* w = E.ws;
-  const int lane = threadIdx.x;
-  if (upred)
-    for (int i = lane; i < P.U * P.d; i += 128) upred[(size_t)e * P.U * P.d + i] = w[L.upred + i];
-  if (xpred)
-    for (int i = lane; i < P.T * P.n; i += 128) xpred[(size_t)e * P.T * P.n + i] = w[L.xpred + i];
-  if (bw)
-    for (int i = lane; i < P.nbranch - 1; i += 128) bw[(size_t)e * (P.nbranch - 1) + i] = w[L.w + 1 + i];
-  if (lane == 0) {
-    if (J) J[e] = w[L.sol + P.oJ];
-    if (status) status[e] = r.exit_flag;
-    if (iters) iters[e] = r.iters;
-  }
+  write_outputs<128>(P, L, E.ws, e, E.ws + L.sol + P.oJ, r, upred, xpred, bw, J, status, iters);
 }
 #endif
 
@@ -381,19 +372,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const auto ex = solver_exec<M::kTransform, TL>(P, lds_dyn);
   EgoView E{ws + L.stride * (size_t)e, pol + (size_t)e * P.m};
   IpmResult r = solve_ego_ipm<DevExecT<M::kTransform, TL>, M>(ex, P, L, E);
-  const double* w = E.ws;
-  const int lane = threadIdx.x;
-  if (upred)
-    for (int i = lane; i < P.U * P.d; i += 64) upred[(size_t)e * P.U * P.d + i] = w[L.upred + i];
-  if (xpred)
-    for (int i = lane; i < P.T * P.n; i += 64) xpred[(size_t)e * P.T * P.n + i] = w[L.xpred + i];
-  if (bw)
-    for (int i = lane; i < P.nbranch - 1; i += 64) bw[(size_t)e * (P.nbranch - 1) + i] = w[L.w + 1 + i];
-  if (lane == 0) {
-    if (J) J[e] = w[L.sol + P.oJ];
-    if (status) status[e] = r.exit_flag;
-    if (iters) iters[e] = r.iters;
-  }
+  write_outputs<64>(P, L, E.ws, e, E.ws + L.sol + P.oJ, r, upred, xpred, bw, J, status, iters);
 }
 
 template <class M, bool TL>
@@ -408,19 +387,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const auto ex = solver_exec<false, TL>(P, lds_dyn);
   EgoView E{ws + L.stride * (size_t)e, pol + (size_t)e * P.m};
   IpmResult r = solve_ego_qp<DevExecT<false, TL>, M>(ex, P, L, E);
-  const double* w = E.ws;
-  const int lane = threadIdx.x;
-  if (upred)
-    for (int i = lane; i < P.U * P.d; i += 64) upred[(size_t)e * P.U * P.d + i] = w[L.upred + i];
-  if (xpred)
-    for (int i = lane; i < P.T * P.n; i += 64) xpred[(size_t)e * P.T * P.n + i] = w[L.xpred + i];
-  if (bw)
-    for (int i = lane; i < P.nbranch - 1; i += 64) bw[(size_t)e * (P.nbranch - 1) + i] = w[L.w + 1 + i];
-  if (lane == 0) {
-    if (J) J[e] = r.pcost;
-    if (status) status[e] = r.exit_flag;
-    if (iters) iters[e] = r.iters;
-  }
+  write_outputs<64>(P, L, E.ws, e, &r.pcost, r, upred, xpred, bw, J, status, iters);
 }
 
 // The three parts of a k_loop step as calls of their own: each gets its registers allocated
@@ -556,18 +523,15 @@ struct SolveLaunch {
   int cus = 256;                     // compute units of the device (k_tree's register budget)
   const Plan* hplan = nullptr;       // the plan on the host (launch sizes)
   size_t blk_hot_off = 0;            // ... their LDS offset (doubles)
-#if defined(BMPC_WITH_PHASED)
-  // phase-per-kernel IPM (experimental/bmpc_dev_ph.h, tools-only builds): per-iteration "egos
-  // going on" counters, their pinned read-back slot, the iteration limit, the sub-batch streams
-  int32_t* d_count = nullptr;
-  int32_t* h_count = nullptr;
-  int maxit = 0;
-  int ph_mode = 1;   // 1: one kernel per phase, 2: one kernel calling grouped out-of-line phases
-  int nsub = 1;                   // mode 1: sub-batches, one stream each
-  hipStream_t* sub = nullptr;     // their streams [kMaxSub]
-  hipEvent_t* sub_ev = nullptr;   // [kMaxSub + 1] fork / join events
-#endif
+  const struct PhasedLaunch* ph = nullptr;   // tools-only builds (BMPC_WITH_PHASED, below)
 };
+using LaunchFn = hipError_t(const SolveLaunch&);
+
+// dynamic LDS above 64 KB needs the kernel's opt-in (a driver call: nothing below that size)
+inline hipError_t optin_lds(const void* kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 
 template <class M>
 hipError_t launch_tree(const SolveLaunch& a) {
@@ -580,15 +544,13 @@ hipError_t launch_tree(const SolveLaunch& a) {
   return hipGetLastError();
 }
 
+// a kernel of the solver signature (k_ipm, k_qp, k_ipm_w2): one workgroup of nt lanes per ego
 template <class K>
-hipError_t launch_solver_kernel(K kernel, const SolveLaunch& a) {
-  if (a.lds_bytes > 64 * 1024) {   // dynamic LDS above 64 KB needs the per-kernel opt-in
-    const hipError_t e =
-        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(a.batch), dim3(64), a.lds_bytes, a.stream, a.bundle, a.ws, a.pol, a.upred,
-                     a.xpred, a.bw, a.J, a.status, a.iters, a.batch);
+hipError_t launch_solver_kernel(K kernel, const SolveLaunch& a, int nt, size_t lds) {
+  const hipError_t e = optin_lds((const void*)kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(a.batch), dim3(nt), lds, a.stream, a.bundle, a.ws, a.pol, a.upred, a.xpred, a.bw,
+                     a.J, a.status, a.iters, a.batch);
   return hipGetLastError();
 }
 
@@ -596,23 +558,17 @@ hipError_t launch_solver_kernel(K kernel, const SolveLaunch& a) {
 template <class M, bool WITH_QP>
 hipError_t launch_solver(const SolveLaunch& a) {
   if constexpr (WITH_QP) {
-    if (a.qp) return a.rich ? launch_solver_kernel(k_qp<M, true>, a) : launch_solver_kernel(k_qp<M, false>, a);
+    if (a.qp)
+      return a.rich ? launch_solver_kernel(k_qp<M, true>, a, 64, a.lds_bytes)
+                    : launch_solver_kernel(k_qp<M, false>, a, 64, a.lds_bytes);
   }
 #if defined(BMPC_BLK2)
-  if (const char* e = getenv("BMPC_IPM_W2")) {
-    if (atoi(e) == 1) {
-      const size_t lds = solver_lds_bytes_blk(*a.hplan, M::kTransform, 2);
-      if (lds > 64 * 1024) {
-        const hipError_t he = hipFuncSetAttribute((const void*)k_ipm_w2<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (he != hipSuccess) return he;
-      }
-      hipLaunchKernelGGL(k_ipm_w2<M>, dim3(a.batch), dim3(128), lds, a.stream, a.bundle, a.ws, a.pol, a.upred,
-                         a.xpred, a.bw, a.J, a.status, a.iters, a.batch);
-      return hipGetLastError();
-    }
-  }
+  if (const char* e = getenv("BMPC_IPM_W2"))
+    if (atoi(e) == 1)
+      return launch_solver_kernel(k_ipm_w2<M>, a, 128, solver_lds_bytes_blk(*a.hplan, M::kTransform, 2));
 #endif
-  return a.rich ? launch_solver_kernel(k_ipm<M, true>, a) : launch_solver_kernel(k_ipm<M, false>, a);
+  return a.rich ? launch_solver_kernel(k_ipm<M, true>, a, 64, a.lds_bytes)
+                : launch_solver_kernel(k_ipm<M, false>, a, 64, a.lds_bytes);
 }
 
 // the fused closed loop (k_loop): the one-wave IPM's LDS and register budget
@@ -620,10 +576,8 @@ template <class M, class SC>
 hipError_t launch_loop(const SolveLaunch& a, const SC& sc, int t0, int nsteps, double* scene, double* stats) {
   void (*k)(const Bundle*, double*, bmpc_policy*, SC, int, int, double*, double*, double*, double*, double*, double*,
             int32_t*, int32_t*, double*, int) = a.rich ? k_loop<M, true, SC> : k_loop<M, false, SC>;
-  if (a.lds_bytes > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = optin_lds((const void*)k, a.lds_bytes);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(a.batch), dim3(64), a.lds_bytes, a.stream, a.bundle, a.ws, const_cast<bmpc_policy*>(a.pol),
                      sc, t0, nsteps, scene, a.upred, const_cast<double*>(a.x), const_cast<double*>(a.z),
                      const_cast<double*>(a.xref), a.J, a.status, a.iters, stats, a.batch);
@@ -638,8 +592,7 @@ hipError_t launch_blk_kernel(const SolveLaunch& a) {
   static size_t opted[16] = {};
   int dev = 0;
   if (a.lds_bytes > 64 * 1024 && hipGetDevice(&dev) == hipSuccess && a.lds_bytes > opted[dev & 15]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_solve_blk<M, QP, NW>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
+    const hipError_t e = optin_lds((const void*)k_solve_blk<M, QP, NW>, a.lds_bytes);
     if (e != hipSuccess) return e;
     opted[dev & 15] = a.lds_bytes;
   }
@@ -647,40 +600,52 @@ hipError_t launch_blk_kernel(const SolveLaunch& a) {
                      a.pol, a.upred, a.xpred, a.bw, a.J, a.status, a.iters, a.batch, a.blk_lay, a.blk_hot_off);
   return hipGetLastError();
 }
+#ifndef BMPC_BLK_ALLOW2
+#define BMPC_BLK_ALLOW2 0
+#endif
+// tools-only A/B (-DBMPC_BLK_ALLOW2): BMPC_BLOCK_WAVES=2 runs the small-batch kernel on two waves per ego
+constexpr bool kAllowTwoWaves = BMPC_BLK_ALLOW2 != 0;
 // (the OSQP-class controllers never take this path: bmpc_hip.hip chooses it for the CVaR IPM only)
 template <class M, bool WITH_QP>
 hipError_t launch_solver_blk(const SolveLaunch& a) {
   if (a.qp) return hipErrorInvalidValue;
-#if defined(BMPC_BLK_ALLOW2)   // tools-only A/B: two waves per ego (BMPC_BLOCK_WAVES=2)
-  if (a.nw == 2) return launch_blk_kernel<M, false, 2>(a);
-#endif
+  if constexpr (kAllowTwoWaves) {
+    if (a.nw == 2) return launch_blk_kernel<M, false, 2>(a);
+  }
   return a.nw == 8 ? launch_blk_kernel<M, false, 8>(a) : launch_blk_kernel<M, false, 4>(a);
 }
 
-// the per-model launchers (bmpc_k_highway.hip, bmpc_k_highway_t.hip, bmpc_k_merge.hip,
-// bmpc_k_quadruped.hip)
-hipError_t launch_tree_highway(const SolveLaunch& a);
-hipError_t launch_solver_highway(const SolveLaunch& a);
-hipError_t launch_tree_highway_t(const SolveLaunch& a);
-hipError_t launch_solver_highway_t(const SolveLaunch& a);
-hipError_t launch_tree_merge(const SolveLaunch& a);
-hipError_t launch_solver_merge(const SolveLaunch& a);
-hipError_t launch_tree_quadruped(const SolveLaunch& a);
-hipError_t launch_solver_quadruped(const SolveLaunch& a);
-hipError_t launch_solver_blk_highway(const SolveLaunch& a);
-hipError_t launch_solver_blk_highway_t(const SolveLaunch& a);
-hipError_t launch_solver_blk_merge(const SolveLaunch& a);
-hipError_t launch_solver_blk_quadruped(const SolveLaunch& a);
+// The launchers of one model, as bmpc_hip.hip's launchers_for hands them out: the solve's tree and
+// solver launches (bmpc_k_<model>.hip) and the small-batch solver (bmpc_kb_<model>.hip, built with
+// BMPC_FLAT_SLAB).
+struct ModelLaunchers {
+  LaunchFn *tree, *solver, *solver_blk;
+  LaunchFn* phased;   // the phase-per-kernel IPM of tools-only builds, or null
+};
+LaunchFn launch_tree_highway, launch_solver_highway, launch_solver_blk_highway;
+LaunchFn launch_tree_highway_t, launch_solver_highway_t, launch_solver_blk_highway_t;
+LaunchFn launch_tree_merge, launch_solver_merge, launch_solver_blk_merge;
+LaunchFn launch_tree_quadruped, launch_solver_quadruped, launch_solver_blk_quadruped;
+// the fused closed loops (bmpc_k_highway.hip, bmpc_k_merge_loop.hip)
 hipError_t launch_loop_highway(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
                                double* stats);
-// (bmpc_k_merge_loop.hip)
 hipError_t launch_loop_merge(const SolveLaunch& a, const bmpc_merge_env_desc& env, const MergeRef& ref, int t0,
                              int nsteps, double* scene, double* stats);
+
 #if defined(BMPC_WITH_PHASED)
-// the phase-per-kernel CVaR IPM (experimental/bmpc_kp_*.hip; tools-only builds with -DBMPC_WITH_PHASED)
-hipError_t launch_ipm_phased_highway(const SolveLaunch& a);
-hipError_t launch_ipm_phased_highway_t(const SolveLaunch& a);
-hipError_t launch_ipm_phased_merge(const SolveLaunch& a);
+// The phase-per-kernel CVaR IPM (experimental/bmpc_dev_ph.h, bmpc_kp_*.hip; tools-only builds with
+// -DBMPC_WITH_PHASED): what a launch of it takes beyond SolveLaunch, and its per-model launchers.
+constexpr int kMaxSub = 8;   // sub-batch streams
+struct PhasedLaunch {
+  int32_t* d_count = nullptr;   // egos going on per iteration [kMaxSub][maxit + 1]
+  int32_t* h_count = nullptr;   // ... pinned read-back slots [kMaxSub]
+  int maxit = 0;
+  int ph_mode = 1;   // 1: one kernel per phase, 2: one kernel calling grouped out-of-line phases
+  int nsub = 1;                   // mode 1: sub-batches, one stream each
+  hipStream_t sub[kMaxSub] = {};   // their streams
+  hipEvent_t sub_ev[kMaxSub + 1] = {};   // fork / join events
+};
+LaunchFn launch_ipm_phased_highway, launch_ipm_phased_highway_t, launch_ipm_phased_merge;
 #endif
 
 }  // namespace dev

@@ -19,15 +19,6 @@
 using namespace bmpc;
 using namespace bmpc::dev;
 
-#if defined(BMPC_WITH_PHASED)
-#ifndef BMPC_IPM_PHASED_DEFAULT
-#define BMPC_IPM_PHASED_DEFAULT 0
-#endif
-#ifndef BMPC_PH_STREAMS_DEFAULT
-#define BMPC_PH_STREAMS_DEFAULT 4
-#endif
-#endif
-
 namespace {
 
 // LDS-rich launch (topology tables and coupling system in LDS) only when it costs no
@@ -231,6 +222,63 @@ struct QPCacheEntry {
   GrowBuf tab;
   uint64_t used = 0;
 };
+
+// A plan's share of the phase-per-kernel IPM (experimental/bmpc_dev_ph.h: mode 1 one kernel per
+// IPM phase, the factored coupling system re-read into LDS by every kernel that solves with it;
+// modes 2 / 3 one kernel calling grouped phase functions).  Tools-only builds; the product's
+// plans carry the empty stand-in.
+#if defined(BMPC_WITH_PHASED)
+#ifndef BMPC_IPM_PHASED_DEFAULT
+#define BMPC_IPM_PHASED_DEFAULT 0
+#endif
+#ifndef BMPC_PH_STREAMS_DEFAULT
+#define BMPC_PH_STREAMS_DEFAULT 4
+#endif
+#define BMPC_PHASED_FN(model) launch_ipm_phased_##model
+struct PhasedPlan {
+  PhasedLaunch l;
+  int create(int maxit) {
+    l.maxit = maxit;
+    if (hipMalloc(&l.d_count, sizeof(int32_t) * kMaxSub * (size_t)(maxit + 1)) != hipSuccess ||
+        hipHostMalloc(&l.h_count, sizeof(int32_t) * kMaxSub) != hipSuccess)
+      return fail(-12, "hipMalloc failed (out of device memory?)");
+    for (auto& q : l.sub)
+      if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return fail(-5, "hipStreamCreate failed");
+    for (auto& e : l.sub_ev)
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(-5, "hipEventCreate failed");
+    return 0;
+  }
+  void destroy() {
+    hipFree(l.d_count);
+    if (l.h_count) hipHostFree(l.h_count);
+    for (auto& q : l.sub)
+      if (q) {
+        hipStreamSynchronize(q);
+        hipStreamDestroy(q);
+      }
+    for (auto& e : l.sub_ev)
+      if (e) hipEventDestroy(e);
+  }
+  // The launch's phased part: BMPC_IPM_PHASED (0: monolithic k_ipm) and BMPC_PH_STREAMS (mode 1's
+  // sub-batch streams; 1 = all on the solve's stream).  Large LDS-rich CVaR batches (`eligible`)
+  // of a model that has it take the phased launcher instead of `solver`.
+  void fill(SolveLaunch& a, bool eligible, LaunchFn*& solver, LaunchFn* phased) {
+    const char* e = getenv("BMPC_IPM_PHASED");
+    l.ph_mode = e ? atoi(e) : BMPC_IPM_PHASED_DEFAULT;
+    e = getenv("BMPC_PH_STREAMS");
+    l.nsub = e ? atoi(e) : BMPC_PH_STREAMS_DEFAULT;
+    a.ph = &l;
+    if (eligible && phased && l.ph_mode != 0) solver = phased;
+  }
+};
+#else
+#define BMPC_PHASED_FN(model) nullptr
+struct PhasedPlan {
+  int create(int) { return 0; }
+  void destroy() {}
+  void fill(SolveLaunch&, bool, LaunchFn*&, LaunchFn*) {}
+};
+#endif
 }  // namespace
 
 struct bmpc_ctx {
@@ -292,13 +340,22 @@ struct bmpc_plan {
   bmpc_merge_env_desc menv = {};
   double* d_mref = nullptr;
   int n_mref = 0;   // 0: no merge scene set
-#if defined(BMPC_WITH_PHASED)
-  int32_t* d_count = nullptr;   // phase-per-kernel IPM: egos going on per iteration [kMaxSub][maxit + 1]
-  int32_t* h_count = nullptr;   // ... pinned read-back slots [kMaxSub]
-  hipStream_t sub[kMaxSub] = {};   // ... its sub-batch streams
-  hipEvent_t sub_ev[kMaxSub + 1] = {};
-#endif
+  PhasedPlan ph;   // (empty but in tools-only builds)
 };
+
+// the stream a call works on: the caller's, remembered for drain(), or the plan's own
+static hipStream_t plan_stream(bmpc_plan* pl, void* stream) {
+  if (stream) pl->user_stream = (hipStream_t)stream;
+  return stream ? (hipStream_t)stream : pl->stream;
+}
+
+// waits for the plan's stream, then for the last caller stream: whoever rewrites device state
+// that launches read (policies, lane references, scene tables) drains first
+static int drain(bmpc_plan* pl) {
+  HIPCHECK(hipStreamSynchronize(pl->stream));
+  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  return 0;
+}
 
 // the plan's constants and layout, with the table and lane-reference pointers at their device
 // copies, into the device Bundle the kernels read
@@ -368,11 +425,6 @@ int bmpc_plan_create(bmpc_ctx* ctx, const bmpc_plan_desc* desc, int batch, bmpc_
       hipMalloc(&pl->d_out, sizeof(double) * (size_t)batch * ((size_t)P.U * P.d + (size_t)P.T * P.n + P.nbranch + 1)) != hipSuccess ||
       hipMalloc(&pl->d_iout, sizeof(int32_t) * (size_t)batch * 2) != hipSuccess)
     return cleanup(fail(-12, "hipMalloc failed (out of device memory?)"));
-#if defined(BMPC_WITH_PHASED)
-  if (hipMalloc(&pl->d_count, sizeof(int32_t) * kMaxSub * (size_t)(P.desc.maxit + 1)) != hipSuccess ||
-      hipHostMalloc(&pl->h_count, sizeof(int32_t) * kMaxSub) != hipSuccess)
-    return cleanup(fail(-12, "hipMalloc failed (out of device memory?)"));
-#endif
   if (hipMemcpy(pl->d_tables, pl->hp.blob.data(), pl->hp.blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
     return cleanup(fail(-5, "hipMemcpy tables failed"));
   if (upload_bundle(pl) != hipSuccess ||
@@ -385,12 +437,7 @@ int bmpc_plan_create(bmpc_ctx* ctx, const bmpc_plan_desc* desc, int batch, bmpc_
     return cleanup(fail(-5, "hipStreamCreate failed"));
   for (auto& e : pl->ev)
     if (hipEventCreate(&e) != hipSuccess) return cleanup(fail(-5, "hipEventCreate failed"));
-#if defined(BMPC_WITH_PHASED)
-  for (auto& q : pl->sub)
-    if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(-5, "hipStreamCreate failed"));
-  for (auto& e : pl->sub_ev)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return cleanup(fail(-5, "hipEventCreate failed"));
-#endif
+  if (const int rc = pl->ph.create(P.desc.maxit)) return cleanup(rc);
   *out = pl;
   return 0;
 }
@@ -412,17 +459,7 @@ int bmpc_plan_destroy(bmpc_plan* pl) {
   hipFree(pl->d_blk_lay);
   for (auto& e : pl->ev)
     if (e) hipEventDestroy(e);
-#if defined(BMPC_WITH_PHASED)
-  hipFree(pl->d_count);
-  if (pl->h_count) hipHostFree(pl->h_count);
-  for (auto& q : pl->sub)
-    if (q) {
-      hipStreamSynchronize(q);
-      hipStreamDestroy(q);
-    }
-  for (auto& e : pl->sub_ev)
-    if (e) hipEventDestroy(e);
-#endif
+  pl->ph.destroy();
   if (pl->stream) hipStreamDestroy(pl->stream);
   delete pl;
   return 0;
@@ -456,8 +493,7 @@ int bmpc_set_policies(bmpc_plan* pl, const bmpc_policy* pol, const uint8_t* mask
         return fail(-22, "lane-reference (psiref) policies need a HIGHWAY_MERGE plan");
   HIPCHECK(hipSetDevice(pl->ctx->device));
   if (pl->pol_on_device && mask) {   // keep the device-side re-targets of unmasked egos
-    HIPCHECK(hipStreamSynchronize(pl->stream));
-    if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+    if (const int rc = drain(pl)) return rc;
     HIPCHECK(hipMemcpy(pl->h_pol.data(), pl->d_pol, sizeof(bmpc_policy) * pl->h_pol.size(), hipMemcpyDeviceToHost));
   }
   pl->pol_on_device = false;
@@ -475,8 +511,7 @@ int bmpc_set_policies(bmpc_plan* pl, const bmpc_policy* pol, const uint8_t* mask
 int bmpc_get_policies(bmpc_plan* pl, bmpc_policy* pol) {
   if (!pl || !pol) return fail(-22, "null argument");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  HIPCHECK(hipStreamSynchronize(pl->stream));
-  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  if (const int rc = drain(pl)) return rc;
   HIPCHECK(hipMemcpy(pol, pl->d_pol, sizeof(bmpc_policy) * pl->h_pol.size(), hipMemcpyDeviceToHost));
   return 0;
 }
@@ -506,6 +541,18 @@ static int scatter_rows(bmpc_plan* pl, const double* src, size_t off, int cnt, c
   return 0;
 }
 
+// A warm start: host rows [batch][cnt] into the masked egos' slabs at their offsets (null rows
+// are skipped), then those slabs' MISC_INIT flag.
+struct SlabPart { const double* src; size_t off; int cnt; };
+static int scatter_parts(bmpc_plan* pl, std::initializer_list<SlabPart> parts, const uint8_t* mask) {
+  DevBuf dmask;
+  HIPCHECK(upload(dmask, mask, pl->batch));
+  for (const SlabPart& pt : parts)
+    if (int rc = scatter_rows(pl, pt.src, pt.off, pt.cnt, dmask.as<uint8_t>())) return rc;
+  const std::vector<double> ones(pl->batch, 1.0);
+  return scatter_rows(pl, ones.data(), pl->hp.lay.misc + MISC_INIT, 1, dmask.as<uint8_t>());
+}
+
 // Reads back the pending timing events (waits for the last instrumented solve).  The ring is
 // emptied on every exit path: a failed read-back drops the pending samples rather than leaving
 // t_pending at kTimeSlots (the next launch would index past ev[]).
@@ -524,14 +571,6 @@ static int fold_timing(bmpc_plan* pl) {
   }
   return 0;
 }
-
-#if defined(BMPC_WITH_PHASED)
-// 0: monolithic k_ipm, 1: one kernel per IPM phase, 2: one kernel calling grouped phases (k_ipm_g)
-static int use_phased() {
-  const char* e = getenv("BMPC_IPM_PHASED");
-  return e ? atoi(e) : BMPC_IPM_PHASED_DEFAULT;
-}
-#endif
 
 // the flat (generic) address of LDS offset 0: the LDS aperture base every workgroup's LDS is
 // addressed through (the same for every kernel of the process)
@@ -605,10 +644,9 @@ static int blk_layouts(bmpc_plan* pl, size_t lds_base) {
     HIPCHECK(hipMalloc(&pl->d_blk_lay, sizeof(Layout) * (size_t)B));
   } else {
     // a rebuild (the launch's LDS base changed, e.g. BMPC_BLOCK_WAVES toggled between solves):
-    // a small-batch kernel still in flight on the plan's or the caller's stream reads the old
-    // layouts -- let those streams drain before the buffer is overwritten
-    HIPCHECK(hipStreamSynchronize(pl->stream));
-    if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+    // a small-batch kernel still in flight reads the old layouts, on whichever stream a caller
+    // that alternates streams gave it -- let the device drain before the buffer is overwritten
+    HIPCHECK(hipDeviceSynchronize());
   }
   HIPCHECK(hipMemcpy(pl->d_blk_lay, lays.data(), sizeof(Layout) * (size_t)B, hipMemcpyHostToDevice));
   pl->blk_lay_base = lds_base;
@@ -617,102 +655,143 @@ static int blk_layouts(bmpc_plan* pl, size_t lds_base) {
   return 0;
 }
 
-static int launch_solve(bmpc_plan* pl, const double* d_x, const double* d_z, const double* d_xref,
-                        double* d_upred, double* d_xpred, double* d_bw, double* d_J,
-                        int32_t* d_status, int32_t* d_iters, hipStream_t s) {
+// How a plan's solver launches (launch_solve and the fused loops ask here and nowhere else).
+struct LaunchChoice {
+  int nw;             // small-batch launch (k_solve_blk): waves per ego; 0: one wave per ego
+  bool rich;          // LDS-rich or lean (choose_lds_rich; the small-batch kernel is rich)
+  size_t lds_bytes;   // dynamic LDS of the solver kernel (before the small-batch kernel's spans)
+  bool blk_lds;       // small-batch launch: the IPM's arrays in LDS (blk_layouts)
+  bool fused_loop;    // a closed loop runs as one k_loop launch instead of launches per step
+};
+
+// Small batches of the CVaR IPM: one ego per multi-wave workgroup (k_solve_blk) when the batch
+// leaves CUs idle -- 4 waves per ego, 8 for trees of BMPC_BLK_WIDE_T state nodes or more.
+// Measured at one ego (profiles/r03/r03x_blk_waves.log): N=8 NB=2 22 ms vs 30 on one wave,
+// N=20 NB=1 12-14 vs 14-16, N=30 NB=2 44-49 vs 61-65.  BMPC_BLOCK_EGOS: the largest batch that
+// takes this path (default: one ego per CU; 0 disables it); BMPC_BLOCK_WAVES: 4 or 8;
+// BMPC_BLK_LDS=0: the small-batch kernel keeps every array in the slab.
+// Larger CVaR batches may fuse a closed loop into one launch, unless a policy tracks the lane
+// reference or BMPC_LOOP_FUSED=0 asks for the per-step launches (A/B).
+static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform) {
   const Plan& P = pl->hp.plan;
-  const int B = pl->batch;
-  const bool merge = P.desc.model == BMPC_MODEL_HIGHWAY_MERGE;
-  // HIGHWAY plans that take solve's S / Fx / bx run the transform path of the same model
-  const bool hwt = P.desc.model == BMPC_MODEL_HIGHWAY && (P.desc.flags & BMPC_PLAN_TRANSFORM);
-  const bool xform = merge || hwt;
-  const bool tl = choose_lds_rich(P, xform, B, pl->ctx->cus, pl->ctx->lds_per_cu);
-  size_t lds_bytes = solver_lds_bytes(P, xform, tl);
+  const bmpc_ctx* c = pl->ctx;
+  const bool cvar = P.desc.controller == BMPC_CTRL_CVAR;
+  int blk_max = c->cus;
+  if (const char* e = getenv("BMPC_BLOCK_EGOS")) blk_max = atoi(e);
+  LaunchChoice ch{};
+  if (cvar && pl->batch <= blk_max) {
+    ch.nw = P.T >= BMPC_BLK_WIDE_T ? 8 : 4;
+    if (const char* e = getenv("BMPC_BLOCK_WAVES")) ch.nw = atoi(e) == 8 ? 8 : kAllowTwoWaves && atoi(e) == 2 ? 2 : 4;
+    ch.rich = true;
+    ch.lds_bytes = solver_lds_bytes_blk(P, xform, ch.nw);
+    const char* el = getenv("BMPC_BLK_LDS");
+    ch.blk_lds = !(el && atoi(el) == 0);
+    return ch;
+  }
+  ch.rich = choose_lds_rich(P, xform, pl->batch, c->cus, c->lds_per_cu);
+  ch.lds_bytes = solver_lds_bytes(P, xform, ch.rich);
   // occupancy experiments: BMPC_IPM_LDS_BYTES reserves at least that much LDS per workgroup
   // (fewer egos resident per CU => a smaller working set in L2 / Infinity Cache)
   if (const char* e = getenv("BMPC_IPM_LDS_BYTES")) {
     const size_t want = (size_t)atol(e);
-    if (want > lds_bytes && want <= pl->ctx->lds_per_cu) lds_bytes = want;
+    if (want > ch.lds_bytes && want <= c->lds_per_cu) ch.lds_bytes = want;
   }
+  const char* ef = getenv("BMPC_LOOP_FUSED");
+  ch.fused_loop = cvar && !pl->psiref && !(ef && atoi(ef) == 0);
+  return ch;
+}
+
+// one solve launch of the plan as chosen, on stream s
+static SolveLaunch solve_launch(const bmpc_plan* pl, const LaunchChoice& ch, hipStream_t s, const double* d_x,
+                                const double* d_z, const double* d_xref, double* d_upred, double* d_xpred,
+                                double* d_bw, double* d_J, int32_t* d_status, int32_t* d_iters) {
+  SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, d_xpred, d_bw, d_J, d_status,
+                d_iters, pl->batch, ch.lds_bytes, ch.rich, pl->hp.plan.desc.controller != BMPC_CTRL_CVAR, s};
+  if (ch.nw) a.nw = ch.nw;
+  a.cus = pl->ctx->cus;
+  a.hplan = &pl->hp.plan;
+  return a;
+}
+
+// The timing bracket of an instrumented launch on s: mark 0 before the tree launch, 1 between the
+// two, 2 after the solver (ev[3 slot + k]); mark 2 closes the ring slot and folds a full ring.
+static int timing_mark(bmpc_plan* pl, hipStream_t s, int k) {
+  if (!pl->timing) return 0;
+  if (pl->t_pending < 0 || pl->t_pending >= bmpc_plan::kTimeSlots)
+    return fail(-5, "timing ring out of range (t_pending = " + std::to_string(pl->t_pending) + ")");
+  hipEvent_t* ev = pl->ev + 3 * pl->t_pending;
+  HIPCHECK(hipEventRecord(ev[k], s));
+  if (k == 2 && ++pl->t_pending == bmpc_plan::kTimeSlots) return fold_timing(pl);
+  return 0;
+}
+
+static const ModelLaunchers& launchers_for(const Plan& P) {
+  static const ModelLaunchers hw{launch_tree_highway, launch_solver_highway, launch_solver_blk_highway,
+                                 BMPC_PHASED_FN(highway)},
+      hwt{launch_tree_highway_t, launch_solver_highway_t, launch_solver_blk_highway_t, BMPC_PHASED_FN(highway_t)},
+      mrg{launch_tree_merge, launch_solver_merge, launch_solver_blk_merge, BMPC_PHASED_FN(merge)},
+      quad{launch_tree_quadruped, launch_solver_quadruped, launch_solver_blk_quadruped, nullptr};
+  // HIGHWAY plans that take solve's S / Fx / bx run the transform path of the same model
+  if (P.desc.model == BMPC_MODEL_HIGHWAY) return (P.desc.flags & BMPC_PLAN_TRANSFORM) ? hwt : hw;
+  return P.desc.model == BMPC_MODEL_HIGHWAY_MERGE ? mrg : quad;
+}
+
+static int launch_solve(bmpc_plan* pl, const double* d_x, const double* d_z, const double* d_xref,
+                        double* d_upred, double* d_xpred, double* d_bw, double* d_J,
+                        int32_t* d_status, int32_t* d_iters, hipStream_t s) {
+  const Plan& P = pl->hp.plan;
+  const LaunchChoice ch = choose_launch(pl, plan_takes_transform(P));
   if (pl->psiref && P.nlref == 0)
     return fail(-22, "the plan's policies track a lane reference: set it first (bmpc_set_lane_ref)");
-  if (pl->timing && (pl->t_pending < 0 || pl->t_pending >= bmpc_plan::kTimeSlots))
-    return fail(-5, "timing ring out of range (t_pending = " + std::to_string(pl->t_pending) + ")");
-  const bool qp = P.desc.controller != BMPC_CTRL_CVAR;
-  SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, d_xpred, d_bw, d_J, d_status,
-                d_iters, B, lds_bytes, tl, qp, s};
-  a.cus = pl->ctx->cus;
-  a.hplan = &P;
-  int kernel = qp ? (tl ? BMPC_KERNEL_QP_RICH : BMPC_KERNEL_QP_LEAN) : (tl ? BMPC_KERNEL_IPM_RICH : BMPC_KERNEL_IPM_LEAN);
-  hipError_t (*tree)(const SolveLaunch&) = launch_tree_quadruped;
-  hipError_t (*solver)(const SolveLaunch&) = launch_solver_quadruped;
-  if (hwt) tree = launch_tree_highway_t, solver = launch_solver_highway_t;
-  else if (P.desc.model == BMPC_MODEL_HIGHWAY) tree = launch_tree_highway, solver = launch_solver_highway;
-  else if (merge) tree = launch_tree_merge, solver = launch_solver_merge;
-  // Small batches of the CVaR IPM: one ego per multi-wave workgroup (k_solve_blk) when the batch
-  // leaves CUs idle -- 4 waves per ego, 8 for trees of BMPC_BLK_WIDE_T state nodes or more.
-  // Measured at one ego (profiles/r03/r03x_blk_waves.log): N=8 NB=2 22 ms vs 30 on one wave,
-  // N=20 NB=1 12-14 vs 14-16, N=30 NB=2 44-49 vs 61-65.  BMPC_BLOCK_EGOS: the largest batch that
-  // takes this path (default: one ego per CU; 0 disables it); BMPC_BLOCK_WAVES: 4 or 8.
-  int blk_max = pl->ctx->cus;
-  if (const char* e = getenv("BMPC_BLOCK_EGOS")) blk_max = atoi(e);
-  const bool blk = B <= blk_max && P.desc.controller == BMPC_CTRL_CVAR;
-  if (blk) {
-    a.nw = P.T >= BMPC_BLK_WIDE_T ? 8 : 4;
-#if defined(BMPC_BLK_ALLOW2)
-    if (const char* e = getenv("BMPC_BLOCK_WAVES")) a.nw = atoi(e) == 8 ? 8 : atoi(e) == 2 ? 2 : 4;   // tools-only A/B
-#else
-    if (const char* e = getenv("BMPC_BLOCK_WAVES")) a.nw = atoi(e) == 8 ? 8 : 4;
-#endif
-    a.lds_bytes = solver_lds_bytes_blk(P, xform, a.nw);
-    a.rich = true;
-    // BMPC_BLK_LDS=0: the small-batch kernel keeps every array in the slab
-    const char* el = getenv("BMPC_BLK_LDS");
-    if (!(el && atoi(el) == 0)) {
-      if (const int rc = blk_layouts(pl, a.lds_bytes)) return rc;
-      if (pl->d_blk_lay) {
-        a.blk_lay = pl->d_blk_lay;
-        a.blk_hot_off = pl->blk_hot_off;
-        a.lds_bytes = pl->blk_hot_off * sizeof(double) + pl->blk_hot_bytes;
-      }
+  SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, d_xpred, d_bw, d_J, d_status, d_iters);
+  const ModelLaunchers& ml = launchers_for(P);
+  LaunchFn* solver = ch.nw ? ml.solver_blk : ml.solver;
+  if (ch.nw && ch.blk_lds) {
+    if (const int rc = blk_layouts(pl, a.lds_bytes)) return rc;
+    if (pl->d_blk_lay) {
+      a.blk_lay = pl->d_blk_lay;
+      a.blk_hot_off = pl->blk_hot_off;
+      a.lds_bytes = pl->blk_hot_off * sizeof(double) + pl->blk_hot_bytes;
     }
-    kernel = a.nw == 8 ? BMPC_KERNEL_IPM_BLK8 : BMPC_KERNEL_IPM_BLK4;
-    if (hwt) solver = launch_solver_blk_highway_t;
-    else if (P.desc.model == BMPC_MODEL_HIGHWAY) solver = launch_solver_blk_highway;
-    else if (merge) solver = launch_solver_blk_merge;
-    else solver = launch_solver_blk_quadruped;
   }
-#if defined(BMPC_WITH_PHASED)
-  // tools-only builds: the phase-per-kernel IPM (experimental/bmpc_dev_ph.h, mode 1: the factored
-  // coupling system re-read into LDS by every kernel that solves with it) or one kernel calling
-  // grouped phase functions (mode 2/3), selected by BMPC_IPM_PHASED for large LDS-rich CVaR batches
-  a.d_count = pl->d_count;
-  a.h_count = pl->h_count;
-  a.maxit = P.desc.maxit;
-  a.ph_mode = use_phased();
-  a.sub = pl->sub;
-  a.sub_ev = pl->sub_ev;
-  {   // sub-batch streams of the phase-per-kernel IPM (BMPC_PH_STREAMS; 1 = all on the solve's stream)
-    const char* e = getenv("BMPC_PH_STREAMS");
-    a.nsub = e ? atoi(e) : BMPC_PH_STREAMS_DEFAULT;
-  }
-  if (!blk && !qp && tl && a.ph_mode != 0) {
-    if (hwt) solver = launch_ipm_phased_highway_t;
-    else if (P.desc.model == BMPC_MODEL_HIGHWAY) solver = launch_ipm_phased_highway;
-    else if (merge) solver = launch_ipm_phased_merge;
-  }
-#endif
-  pl->last_kernel = kernel;
-  hipEvent_t* ev = pl->ev + 3 * (pl->timing ? pl->t_pending : 0);
-  if (pl->timing) HIPCHECK(hipEventRecord(ev[0], s));
-  HIPCHECK(tree(a));
-  if (pl->timing) HIPCHECK(hipEventRecord(ev[1], s));
+  pl->ph.fill(a, !ch.nw && !a.qp && ch.rich, solver, ml.phased);
+  pl->last_kernel = ch.nw   ? (ch.nw == 8 ? BMPC_KERNEL_IPM_BLK8 : BMPC_KERNEL_IPM_BLK4)
+                    : a.qp  ? (ch.rich ? BMPC_KERNEL_QP_RICH : BMPC_KERNEL_QP_LEAN)
+                            : (ch.rich ? BMPC_KERNEL_IPM_RICH : BMPC_KERNEL_IPM_LEAN);
+  if (const int rc = timing_mark(pl, s, 0)) return rc;
+  HIPCHECK(ml.tree(a));
+  if (const int rc = timing_mark(pl, s, 1)) return rc;
   HIPCHECK(solver(a));
-  if (pl->timing) {
-    HIPCHECK(hipEventRecord(ev[2], s));
-    if (++pl->t_pending == bmpc_plan::kTimeSlots) return fold_timing(pl);
+  return timing_mark(pl, s, 2);
+}
+
+extern "C++" {
+// nsteps closed-loop steps of a scene (bmpc_loop_device, bmpc_merge_loop_device): one k_loop launch
+// (`fused`) for batches that choose_launch lets fuse, otherwise the scene's step (`step`) + the
+// solve launches per step -- same results either way.  retargets: the scene's step rewrites d_pol.
+template <class Step, class Fused>
+static int run_loop(bmpc_plan* pl, bool retargets, int t0, int nsteps, double* d_upred, double* d_x, double* d_z,
+                    double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters, void* stream, Step step,
+                    Fused fused) {
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  hipStream_t s = plan_stream(pl, stream);
+  const LaunchChoice ch = choose_launch(pl, plan_takes_transform(pl->hp.plan));
+  if (!ch.fused_loop) {
+    for (int k = 0; k < nsteps; ++k) {
+      if (int rc = step(t0 + k)) return rc;
+      if (int rc = launch_solve(pl, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters, s)) return rc;
+    }
+    return 0;
   }
-  return 0;
+  const SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
+  pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
+  // (the whole fused launch is booked as the solver's time, none as the tree's)
+  if (const int rc = timing_mark(pl, s, 0)) return rc;
+  if (const int rc = timing_mark(pl, s, 1)) return rc;
+  HIPCHECK(fused(a));
+  if (retargets) pl->pol_on_device = true;
+  return timing_mark(pl, s, 2);
+}
 }
 
 int bmpc_solve(bmpc_plan* pl, const double* x, const double* z, const double* xref, double* upred,
@@ -751,8 +830,7 @@ int bmpc_solve_device(bmpc_plan* pl, const double* d_x, const double* d_z, const
                       int32_t* d_status, int32_t* d_iters, void* stream) {
   if (!pl || !d_x || !d_z || !d_xref) return fail(-22, "null argument");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-  if (stream) pl->user_stream = s;   // (synchronised before the plan's device state is rewritten)
+  hipStream_t s = plan_stream(pl, stream);
   return launch_solve(pl, d_x, d_z, d_xref, d_upred, d_xpred, d_branch_w, d_J, d_status, d_iters, s);
 }
 
@@ -766,8 +844,7 @@ int bmpc_env_step(bmpc_plan* pl, const bmpc_env_desc* env, int t, double* d_scen
   if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_env_step: t > 0 needs the last uPred");
   if (env->n_lane < 1) return fail(-22, "bmpc_env_step: n_lane < 1");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-  if (stream) pl->user_stream = s;
+  hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env, dim3((pl->batch + 63) / 64), dim3(64), 0, s, *env, P.desc.dt, P.N, P.m, P.U, P.d, t,
                      pl->batch, d_scene, pl->d_pol, d_upred, d_J, d_status, d_iters,
                      P.desc.controller == BMPC_CTRL_CVAR ? 1 : 0, d_x, d_z, d_xref, d_stats);
@@ -776,8 +853,6 @@ int bmpc_env_step(bmpc_plan* pl, const bmpc_env_desc* env, int t, double* d_scen
   return 0;
 }
 
-// nsteps closed-loop steps (include/bmpc.h): one k_loop launch for CVaR batches that take the
-// one-wave IPM, otherwise bmpc_env_step + the solve launches per step (same results either way)
 int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps, double* d_scene, double* d_upred,
                      double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
                      double* d_stats, void* stream) {
@@ -790,43 +865,12 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
     return fail(-22, "bmpc_loop_device: CVaR or robust controllers only");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_loop_device: nsteps >= 1 and t0 >= 0");
   if (env->n_lane < 1) return fail(-22, "bmpc_loop_device: n_lane < 1");
-  HIPCHECK(hipSetDevice(pl->ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-  if (stream) pl->user_stream = s;
-  const int B = pl->batch;
-  int blk_max = pl->ctx->cus;   // the small-batch path of launch_solve
-  if (const char* e = getenv("BMPC_BLOCK_EGOS")) blk_max = atoi(e);
-  bool fused = P.desc.controller == BMPC_CTRL_CVAR && B > blk_max && !pl->psiref;
-  if (const char* e = getenv("BMPC_LOOP_FUSED")) fused = fused && atoi(e) != 0;   // 0: per-step launches (A/B)
-  if (!fused) {
-    for (int k = 0; k < nsteps; ++k) {
-      if (int rc = bmpc_env_step(pl, env, t0 + k, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats,
-                                 stream))
-        return rc;
-      if (int rc = launch_solve(pl, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters, s)) return rc;
-    }
-    return 0;
-  }
-  if (pl->timing && (pl->t_pending < 0 || pl->t_pending >= bmpc_plan::kTimeSlots))
-    return fail(-5, "timing ring out of range (t_pending = " + std::to_string(pl->t_pending) + ")");
-  const bool tl = choose_lds_rich(P, false, B, pl->ctx->cus, pl->ctx->lds_per_cu);
-  SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status,
-                d_iters, B, solver_lds_bytes(P, false, tl), tl, false, s};
-  a.cus = pl->ctx->cus;
-  a.hplan = &P;
-  pl->last_kernel = tl ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
-  hipEvent_t* ev = pl->ev + 3 * (pl->timing ? pl->t_pending : 0);
-  if (pl->timing) {   // (the whole fused launch is booked as the solver's time, none as the tree's)
-    HIPCHECK(hipEventRecord(ev[0], s));
-    HIPCHECK(hipEventRecord(ev[1], s));
-  }
-  HIPCHECK(launch_loop_highway(a, *env, t0, nsteps, d_scene, d_stats));
-  pl->pol_on_device = true;
-  if (pl->timing) {
-    HIPCHECK(hipEventRecord(ev[2], s));
-    if (++pl->t_pending == bmpc_plan::kTimeSlots) return fold_timing(pl);
-  }
-  return 0;
+  return run_loop(
+      pl, true, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      [&](int t) {
+        return bmpc_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
+      },
+      [&](const SolveLaunch& a) { return launch_loop_highway(a, *env, t0, nsteps, d_scene, d_stats); });
 }
 
 int bmpc_set_merge_scene(bmpc_plan* pl, const bmpc_merge_env_desc* desc, int nref, const double* grid,
@@ -843,8 +887,7 @@ int bmpc_set_merge_scene(bmpc_plan* pl, const bmpc_merge_env_desc* desc, int nre
   }
   if (desc->n_lane < 1 || desc->merge_lane < 1) return fail(-22, "bmpc_set_merge_scene: n_lane, merge_lane >= 1");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  HIPCHECK(hipStreamSynchronize(pl->stream));   // no scene step in flight reads the old tables
-  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  if (const int rc = drain(pl)) return rc;   // no scene step in flight reads the old tables
   DevBuf fresh;
   HIPCHECK(fresh.alloc(sizeof(double) * 3 * (size_t)nref));
   const double* parts[] = {grid, refY, refpsi};
@@ -865,8 +908,7 @@ int bmpc_merge_env_step(bmpc_plan* pl, int t, double* d_scene, const double* d_u
   if (!pl->n_mref) return fail(-22, "bmpc_merge_env_step: no merge scene (bmpc_set_merge_scene)");
   if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_merge_env_step: t > 0 needs the last uPred");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-  if (stream) pl->user_stream = s;
+  hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env_merge, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, pl->menv,
                      MergeRef{pl->d_mref, pl->n_mref}, t, pl->batch, d_scene, pl->d_ws, d_upred, d_J, d_status, d_iters,
                      d_x, d_z, d_xref, d_stats);
@@ -874,7 +916,6 @@ int bmpc_merge_env_step(bmpc_plan* pl, int t, double* d_scene, const double* d_u
   return 0;
 }
 
-// nsteps closed-loop merge steps (include/bmpc.h): bmpc_loop_device's launch rule and bookkeeping
 int bmpc_merge_loop_device(bmpc_plan* pl, int t0, int nsteps, double* d_scene, double* d_upred, double* d_x,
                            double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
                            double* d_stats, void* stream) {
@@ -882,43 +923,14 @@ int bmpc_merge_loop_device(bmpc_plan* pl, int t0, int nsteps, double* d_scene, d
     return fail(-22, "null argument");
   if (!pl->n_mref) return fail(-22, "bmpc_merge_loop_device: no merge scene (bmpc_set_merge_scene)");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_merge_loop_device: nsteps >= 1 and t0 >= 0");
-  const Plan& P = pl->hp.plan;
-  HIPCHECK(hipSetDevice(pl->ctx->device));
-  hipStream_t s = stream ? (hipStream_t)stream : pl->stream;
-  if (stream) pl->user_stream = s;
-  const int B = pl->batch;
-  int blk_max = pl->ctx->cus;   // the small-batch path of launch_solve
-  if (const char* e = getenv("BMPC_BLOCK_EGOS")) blk_max = atoi(e);
-  bool fused = B > blk_max && !pl->psiref;   // (a merge scene's plan is a CVaR plan)
-  if (const char* e = getenv("BMPC_LOOP_FUSED")) fused = fused && atoi(e) != 0;   // 0: per-step launches (A/B)
-  if (!fused) {
-    for (int k = 0; k < nsteps; ++k) {
-      if (int rc = bmpc_merge_env_step(pl, t0 + k, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats,
-                                       stream))
-        return rc;
-      if (int rc = launch_solve(pl, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters, s)) return rc;
-    }
-    return 0;
-  }
-  if (pl->timing && (pl->t_pending < 0 || pl->t_pending >= bmpc_plan::kTimeSlots))
-    return fail(-5, "timing ring out of range (t_pending = " + std::to_string(pl->t_pending) + ")");
-  const bool tl = choose_lds_rich(P, true, B, pl->ctx->cus, pl->ctx->lds_per_cu);
-  SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status,
-                d_iters, B, solver_lds_bytes(P, true, tl), tl, false, s};
-  a.cus = pl->ctx->cus;
-  a.hplan = &P;
-  pl->last_kernel = tl ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
-  hipEvent_t* ev = pl->ev + 3 * (pl->timing ? pl->t_pending : 0);
-  if (pl->timing) {   // (the whole fused launch is booked as the solver's time, none as the tree's)
-    HIPCHECK(hipEventRecord(ev[0], s));
-    HIPCHECK(hipEventRecord(ev[1], s));
-  }
-  HIPCHECK(launch_loop_merge(a, pl->menv, MergeRef{pl->d_mref, pl->n_mref}, t0, nsteps, d_scene, d_stats));
-  if (pl->timing) {
-    HIPCHECK(hipEventRecord(ev[2], s));
-    if (++pl->t_pending == bmpc_plan::kTimeSlots) return fold_timing(pl);
-  }
-  return 0;
+  return run_loop(
+      pl, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      [&](int t) {
+        return bmpc_merge_env_step(pl, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
+      },
+      [&](const SolveLaunch& a) {
+        return launch_loop_merge(a, pl->menv, MergeRef{pl->d_mref, pl->n_mref}, t0, nsteps, d_scene, d_stats);
+      });
 }
 
 static int gather(bmpc_plan* pl, size_t off, int count, double* host) {
@@ -963,19 +975,8 @@ int bmpc_set_warm_start(bmpc_plan* pl, const double* uLin, const double* p, cons
   HIPCHECK(hipSetDevice(pl->ctx->device));
   const Plan& P = pl->hp.plan;
   const Layout& L = pl->hp.lay;
-  const int B = pl->batch;
-  DevBuf dmask;
-  HIPCHECK(upload(dmask, mask, B));
-  std::vector<double> ones(B, 1.0);
-  struct Part { const double* src; size_t off; int cnt; };
-  const Part parts[] = {{uLin, L.uLin, (P.U + 1) * P.d},
-                        {p, L.pprev, P.bdim * P.m},
-                        {jcons, L.misc + MISC_JCONS, 1},
-                        {old_input, L.misc + MISC_OLDU, P.d},
-                        {ones.data(), L.misc + MISC_INIT, 1}};
-  for (const Part& pt : parts)
-    if (int rc = scatter_rows(pl, pt.src, pt.off, pt.cnt, dmask.as<uint8_t>())) return rc;
-  return 0;
+  return scatter_parts(pl, {{uLin, L.uLin, (P.U + 1) * P.d}, {p, L.pprev, P.bdim * P.m},
+                            {jcons, L.misc + MISC_JCONS, 1}, {old_input, L.misc + MISC_OLDU, P.d}}, mask);
 }
 
 int bmpc_get_robust_warm_start(bmpc_plan* pl, double* xLin, double* uLin, double* old_input) {
@@ -998,18 +999,8 @@ int bmpc_set_robust_warm_start(bmpc_plan* pl, const double* xLin, const double* 
   HIPCHECK(hipSetDevice(pl->ctx->device));
   const Plan& P = pl->hp.plan;
   const Layout& L = pl->hp.lay;
-  const int B = pl->batch;
-  DevBuf dmask;
-  HIPCHECK(upload(dmask, mask, B));
-  std::vector<double> ones(B, 1.0);
-  struct Part { const double* src; size_t off; int cnt; };
-  const Part parts[] = {{xLin, L.xlin, P.T * P.n},
-                        {uLin, L.uLin, P.U * P.d},
-                        {old_input, L.misc + MISC_OLDU, P.d},
-                        {ones.data(), L.misc + MISC_INIT, 1}};
-  for (const Part& pt : parts)
-    if (int rc = scatter_rows(pl, pt.src, pt.off, pt.cnt, dmask.as<uint8_t>())) return rc;
-  return 0;
+  return scatter_parts(pl, {{xLin, L.xlin, P.T * P.n}, {uLin, L.uLin, P.U * P.d}, {old_input, L.misc + MISC_OLDU, P.d}},
+                       mask);
 }
 
 int bmpc_set_transform(bmpc_plan* pl, const double* S, const uint8_t* s_on, const double* bx, const uint8_t* mask) {
@@ -1063,9 +1054,9 @@ int bmpc_get_transform(bmpc_plan* pl, double* S, double* bx, double* flags) {
   const Plan& P = pl->hp.plan;
   if (!plan_takes_transform(P)) return fail(-22, "bmpc_get_transform: the plan takes no state transformation");
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
-  const Layout& L = pl->hp.lay;
   int rc;
+  if ((rc = drain(pl))) return rc;
+  const Layout& L = pl->hp.lay;
   if ((rc = gather(pl, L.xform + XF_S, P.n * P.n, S))) return rc;
   if ((rc = gather(pl, L.xform + XF_BX, P.nFx, bx))) return rc;
   static_assert(XF_BXSET == XF_SON + 1, "the two flags are gathered as one pair");
@@ -1119,6 +1110,48 @@ int bmpc_timing(bmpc_plan* pl, double* ms, int32_t* count) {
   return 0;
 }
 
+// A packed evaluation call on the context's stream (bmpc_model_eval_ref, bmpc_hmm_eval; the caller
+// holds q_mu): the inputs packed into q_host and uploaded in one copy to the grow-only q_aux, a
+// device slot behind them for every output that has a host array, and -- after the caller's launch
+// -- one read-back, unpacked.  The compat environments and the belief MPC call these once per
+// control step: no allocation and no device-wide synchronisation per call.
+struct PackedArg { const void* host; size_t bytes; };           // (packed as whole doubles)
+struct PackedOut { double* host; size_t len; double* dev; };    // len doubles; dev is null when host is
+struct PackedCall {
+  bmpc_ctx* ctx;
+  PackedOut* out;
+  int nout;
+  size_t tin = 0, tout = 0;
+  int begin(const PackedArg* in, int nin, const double** din) {   // din[i]: in[i] on the device
+    for (int i = 0; i < nin; ++i) tin += (in[i].bytes + sizeof(double) - 1) / sizeof(double);
+    for (int i = 0; i < nout; ++i) tout += out[i].host ? out[i].len : 0;
+    ctx->q_host.resize(tin + tout);
+    HIPCHECK(ctx->q_aux.reserve((tin + tout) * sizeof(double)));
+    if (!ctx->qstream) HIPCHECK(hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking));
+    double* cur = ctx->q_aux.as<double>();
+    for (int i = 0; i < nin; ++i) {
+      if (in[i].bytes) memcpy(ctx->q_host.data() + (cur - ctx->q_aux.as<double>()), in[i].host, in[i].bytes);
+      din[i] = cur;
+      cur += (in[i].bytes + sizeof(double) - 1) / sizeof(double);
+    }
+    HIPCHECK(hipMemcpyAsync(ctx->q_aux.p, ctx->q_host.data(), tin * sizeof(double), hipMemcpyHostToDevice, ctx->qstream));
+    for (int i = 0; i < nout; ++i) {
+      out[i].dev = out[i].host ? cur : nullptr;
+      if (out[i].host) cur += out[i].len;
+    }
+    return 0;
+  }
+  int finish() {   // after the launch
+    HIPCHECK(hipGetLastError());
+    double* h = ctx->q_host.data() + tin;
+    if (tout) HIPCHECK(hipMemcpyAsync(h, ctx->q_aux.as<double>() + tin, tout * sizeof(double), hipMemcpyDeviceToHost, ctx->qstream));
+    HIPCHECK(hipStreamSynchronize(ctx->qstream));
+    for (int i = 0; i < nout; h += out[i].host ? out[i].len : 0, ++i)
+      if (out[i].host) memcpy(out[i].host, h, out[i].len * sizeof(double));
+    return 0;
+  }
+};
+
 int bmpc_model_eval(bmpc_ctx* ctx, const bmpc_plan_desc* desc, const bmpc_policy* policies, int B,
                     const double* x, const double* u, const double* z, double* A, double* Bm,
                     double* C, double* xp, double* p, double* dp, double* zpred, double* h0,
@@ -1145,68 +1178,28 @@ int bmpc_model_eval_ref(bmpc_ctx* ctx, const bmpc_plan_desc* desc, const bmpc_po
       (desc->model != BMPC_MODEL_HIGHWAY && desc->model != BMPC_MODEL_HIGHWAY_MERGE &&
        desc->model != BMPC_MODEL_QUADRUPED) || m < 1 || m > BMPC_MAX_M || N < 1)
     return fail(-22, "bad model dimensions");
-  // one packed upload (policies | x | u | z) and one packed read-back of the requested outputs,
-  // on the context's stream into its grow-only buffer: the compat environments call this once
-  // per control step, so no allocation and no device-wide synchronisation per call
-  const size_t sizes[] = {(size_t)n * n, (size_t)n * d, (size_t)n, (size_t)n, (size_t)m,
-                          (size_t)m * n, (size_t)N * m * n, 1, (size_t)n};
-  double* hosts[] = {A, Bm, C, xp, p, dp, zpred, h0, dh};
-  const bool want[] = {A != nullptr, Bm != nullptr, C != nullptr, xp != nullptr, p != nullptr,
-                       dp != nullptr && p != nullptr, zpred != nullptr, h0 != nullptr, dh != nullptr && h0 != nullptr};
-  const size_t npol = ((size_t)B * m * sizeof(bmpc_policy) + sizeof(double) - 1) / sizeof(double);
-  const size_t tin = npol + (size_t)B * (2 * n + d) + 2 * (size_t)nref;
-  size_t tout = 0;
-  for (int i = 0; i < 9; ++i) tout += want[i] ? (size_t)B * sizes[i] : 0;
+  const size_t Bz = (size_t)B;
+  const PackedArg in[] = {{policies, Bz * m * sizeof(bmpc_policy)}, {x, sizeof(double) * Bz * n},
+                          {u, sizeof(double) * Bz * d},             {z, sizeof(double) * Bz * n},
+                          {grid, sizeof(double) * nref},            {values, sizeof(double) * nref}};
+  // (dp goes with p, dh with h0)
+  PackedOut out[] = {{A, Bz * n * n}, {Bm, Bz * n * d},           {C, Bz * n},         {xp, Bz * n},
+                     {p, Bz * m},     {p ? dp : nullptr, Bz * m * n}, {zpred, Bz * N * m * n}, {h0, Bz},
+                     {h0 ? dh : nullptr, Bz * n}};
+  const double* din[6];
   std::lock_guard<std::mutex> lock(ctx->q_mu);
   HIPCHECK(hipSetDevice(ctx->device));
-  std::vector<double>& hv = ctx->q_host;
-  hv.resize(tin + tout);
-  memcpy(hv.data(), policies, (size_t)B * m * sizeof(bmpc_policy));
-  memcpy(hv.data() + npol, x, sizeof(double) * (size_t)B * n);
-  memcpy(hv.data() + npol + (size_t)B * n, u, sizeof(double) * (size_t)B * d);
-  memcpy(hv.data() + npol + (size_t)B * (n + d), z, sizeof(double) * (size_t)B * n);
-  if (nref) {
-    memcpy(hv.data() + npol + (size_t)B * (2 * n + d), grid, sizeof(double) * nref);
-    memcpy(hv.data() + npol + (size_t)B * (2 * n + d) + nref, values, sizeof(double) * nref);
-  }
-  HIPCHECK(ctx->q_aux.reserve((tin + tout) * sizeof(double)));
-  if (!ctx->qstream) HIPCHECK(hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking));
-  hipStream_t st = ctx->qstream;
-  double* buf = ctx->q_aux.as<double>();
-  HIPCHECK(hipMemcpyAsync(buf, hv.data(), tin * sizeof(double), hipMemcpyHostToDevice, st));
-  const bmpc_policy* dpol = reinterpret_cast<const bmpc_policy*>(buf);
-  const double* dxp = buf + npol;
-  const double* dup = dxp + (size_t)B * n;
-  const double* dzp = dup + (size_t)B * d;
-  const double* dref = dzp + (size_t)B * n;
-  const LaneRef R{nref ? dref : nullptr, nref ? dref + nref : nullptr, nref};
-  double* dev[9];
-  double* cur = buf + tin;
-  for (int i = 0; i < 9; ++i) {
-    dev[i] = want[i] ? cur : nullptr;
-    if (want[i]) cur += (size_t)B * sizes[i];
-  }
-  if (desc->model == BMPC_MODEL_HIGHWAY)
-    hipLaunchKernelGGL(k_model<Highway>, dim3((B + 63) / 64), dim3(64), 0, st, *desc, dpol, B, dxp, dup,
-                       dzp, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], R);
-  else if (desc->model == BMPC_MODEL_HIGHWAY_MERGE)
-    hipLaunchKernelGGL(k_model<HighwayMerge>, dim3((B + 63) / 64), dim3(64), 0, st, *desc, dpol, B, dxp, dup,
-                       dzp, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], R);
-  else
-    hipLaunchKernelGGL(k_model<Quadruped>, dim3((B + 63) / 64), dim3(64), 0, st, *desc, dpol, B, dxp, dup,
-                       dzp, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], dev[8], R);
-  HIPCHECK(hipGetLastError());
-  if (tout) HIPCHECK(hipMemcpyAsync(hv.data() + tin, buf + tin, tout * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  const double* o = hv.data() + tin;
-  for (int i = 0; i < 9; ++i)
-    if (want[i]) {
-      memcpy(hosts[i], o, sizeof(double) * (size_t)B * sizes[i]);
-      o += (size_t)B * sizes[i];
-    }
-  return 0;
+  PackedCall pc{ctx, out, 9};
+  if (const int rc = pc.begin(in, 6, din)) return rc;
+  const LaneRef R{nref ? din[4] : nullptr, nref ? din[5] : nullptr, nref};
+  const auto k = desc->model == BMPC_MODEL_HIGHWAY         ? k_model<Highway>
+                 : desc->model == BMPC_MODEL_HIGHWAY_MERGE ? k_model<HighwayMerge>
+                                                           : k_model<Quadruped>;
+  hipLaunchKernelGGL(k, dim3((B + 63) / 64), dim3(64), 0, ctx->qstream, *desc, (const bmpc_policy*)din[0], B, din[1],
+                     din[2], din[3], out[0].dev, out[1].dev, out[2].dev, out[3].dev, out[4].dev, out[5].dev, out[6].dev,
+                     out[7].dev, out[8].dev, R);
+  return pc.finish();
 }
-
 
 int bmpc_set_lane_ref(bmpc_plan* pl, int nref, const double* grid, const double* values) {
   if (!pl) return fail(-22, "null argument");
@@ -1216,8 +1209,7 @@ int bmpc_set_lane_ref(bmpc_plan* pl, int nref, const double* grid, const double*
     if (!e.empty()) return fail(-22, e);
   }
   HIPCHECK(hipSetDevice(pl->ctx->device));
-  HIPCHECK(hipStreamSynchronize(pl->stream));   // no solve in flight reads the old reference
-  if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
+  if (const int rc = drain(pl)) return rc;   // no solve in flight reads the old reference
   // the new copy is built beside the old one and swapped in only once the device bundle points
   // at it: a failure on the way leaves the plan on its old, still allocated reference
   DevBuf fresh;
@@ -1247,55 +1239,18 @@ int bmpc_hmm_eval(bmpc_ctx* ctx, int M, int m, const double* hc, int B, const do
                   double* Jh) {
   if (!ctx || !hc || !xb || !u || !xbackup || B <= 0) return fail(-22, "null argument");
   if (M < 1 || m < 1 || M > HMM_MAX_AGENTS || m > HMM_MAX_BACKUPS) return fail(-22, "M, m must be in 1..4");
+  const size_t Bz = (size_t)B, nb = 4 + (size_t)M * m, Mm = (size_t)M * m;
+  const PackedArg in[] = {{hc, sizeof(double) * 8}, {xb, sizeof(double) * Bz * nb}, {u, sizeof(double) * Bz * 2},
+                          {xbackup, sizeof(double) * Bz * Mm * 4}};
+  PackedOut out[] = {{xbp, Bz * nb}, {A, Bz * nb * nb}, {Bm, Bz * nb * 2}, {C, Bz * nb}, {h0, Bz * Mm}, {Jh, Bz * Mm * nb}};
+  const double* din[4];
   std::lock_guard<std::mutex> lock(ctx->q_mu);
   HIPCHECK(hipSetDevice(ctx->device));
-  const size_t nb = 4 + (size_t)M * m;
-  const size_t in_sz[] = {8, (size_t)B * nb, (size_t)B * 2, (size_t)B * M * m * 4};
-  const double* in_h[] = {hc, xb, u, xbackup};
-  const size_t out_sz[] = {nb, nb * nb, nb * 2, nb, (size_t)M * m, (size_t)M * m * nb};
-  double* out_h[] = {xbp, A, Bm, C, h0, Jh};
-  // one upload of the packed inputs, one read-back of the packed outputs, on the context's
-  // stream into its grow-only buffer (the belief MPC calls this once per control step)
-  size_t tin = 0, tout = 0;
-  for (size_t v : in_sz) tin += v;
-  for (int i = 0; i < 6; ++i) tout += out_h[i] ? (size_t)B * out_sz[i] : 0;
-  std::vector<double>& hv = ctx->q_host;
-  hv.resize(tin + tout);
-  {
-    double* c = hv.data();
-    for (int i = 0; i < 4; ++i) {
-      memcpy(c, in_h[i], in_sz[i] * sizeof(double));
-      c += in_sz[i];
-    }
-  }
-  HIPCHECK(ctx->q_aux.reserve((tin + tout) * sizeof(double)));
-  if (!ctx->qstream) HIPCHECK(hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking));
-  hipStream_t st = ctx->qstream;
-  double* buf = ctx->q_aux.as<double>();
-  HIPCHECK(hipMemcpyAsync(buf, hv.data(), tin * sizeof(double), hipMemcpyHostToDevice, st));
-  double* din[4];
-  double* cur = buf;
-  for (int i = 0; i < 4; ++i) {
-    din[i] = cur;
-    cur += in_sz[i];
-  }
-  double* dout[6];
-  for (int i = 0; i < 6; ++i) {
-    dout[i] = out_h[i] ? cur : nullptr;
-    if (out_h[i]) cur += (size_t)B * out_sz[i];
-  }
-  hipLaunchKernelGGL(k_hmm, dim3((B + 63) / 64), dim3(64), 0, st, M, m, din[0], B, din[1], din[2], din[3], dout[0],
-                     dout[1], dout[2], dout[3], dout[4], dout[5]);
-  HIPCHECK(hipGetLastError());
-  if (tout) HIPCHECK(hipMemcpyAsync(hv.data() + tin, buf + tin, tout * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipStreamSynchronize(st));
-  const double* o = hv.data() + tin;
-  for (int i = 0; i < 6; ++i)
-    if (out_h[i]) {
-      memcpy(out_h[i], o, (size_t)B * out_sz[i] * sizeof(double));
-      o += (size_t)B * out_sz[i];
-    }
-  return 0;
+  PackedCall pc{ctx, out, 6};
+  if (const int rc = pc.begin(in, 4, din)) return rc;
+  hipLaunchKernelGGL(k_hmm, dim3((B + 63) / 64), dim3(64), 0, ctx->qstream, M, m, din[0], B, din[1], din[2], din[3],
+                     out[0].dev, out[1].dev, out[2].dev, out[3].dev, out[4].dev, out[5].dev);
+  return pc.finish();
 }
 
 int bmpc_qp_solve(bmpc_ctx* ctx, int n, int m, const int32_t* Pp, const int32_t* Pi, const int32_t* Ap,
@@ -1390,7 +1345,7 @@ int bmpc_qp_solve(bmpc_ctx* ctx, int n, int m, const int32_t* Pp, const int32_t*
   d.xmap = d.cscat + h.cscat.size();
   d.ymap = d.xmap + h.xmap.size();
   const size_t lds = bandqp_lds_doubles(d.nk, d.W, d.lb_lds) * sizeof(double);
-  if (lds > 64 * 1024) HIPCHECK(hipFuncSetAttribute((const void*)k_bandqp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIPCHECK(optin_lds((const void*)k_bandqp, lds));
   hipLaunchKernelGGL(k_bandqp, dim3(batch), dim3(64), lds, st, d, ctx->q_in.as<double>(), ctx->q_in.as<double>() + nv,
                      ctx->q_ws.as<double>(), dx, dy, dst, dit, batch);
   HIPCHECK(hipGetLastError());

@@ -80,18 +80,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   } else if constexpr (PH == PH_FIN) {
     const IpmResult r = ph_result(C.ws + L.ist);
     ipm_unpack<X, M>(ex, P, L, ws, r);
-    const int lane = threadIdx.x;
-    if (a.upred)
-      for (int i = lane; i < P.U * P.d; i += 64) a.upred[(size_t)e * P.U * P.d + i] = ws[L.upred + i];
-    if (a.xpred)
-      for (int i = lane; i < P.T * P.n; i += 64) a.xpred[(size_t)e * P.T * P.n + i] = ws[L.xpred + i];
-    if (a.bw)
-      for (int i = lane; i < P.nbranch - 1; i += 64) a.bw[(size_t)e * (P.nbranch - 1) + i] = ws[L.w + 1 + i];
-    if (lane == 0) {
-      if (a.J) a.J[e] = ws[L.sol + P.oJ];
-      if (a.status) a.status[e] = r.exit_flag;
-      if (a.iters) a.iters[e] = r.iters;
-    }
+    write_outputs<64>(P, L, ws, e, ws + L.sol + P.oJ, r, a.upred, a.xpred, a.bw, a.J, a.status, a.iters);
   }
 }
 
@@ -178,49 +167,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
     }
   const IpmResult r = ph_result(st);
   ipm_unpack<X, M>(ex, P, L, ws, r);
-  const int lane = threadIdx.x;
-  if (a.upred)
-    for (int i = lane; i < P.U * P.d; i += 64) a.upred[(size_t)e * P.U * P.d + i] = ws[L.upred + i];
-  if (a.xpred)
-    for (int i = lane; i < P.T * P.n; i += 64) a.xpred[(size_t)e * P.T * P.n + i] = ws[L.xpred + i];
-  if (a.bw)
-    for (int i = lane; i < P.nbranch - 1; i += 64) a.bw[(size_t)e * (P.nbranch - 1) + i] = ws[L.w + 1 + i];
-  if (lane == 0) {
-    if (a.J) a.J[e] = ws[L.sol + P.oJ];
-    if (a.status) a.status[e] = r.exit_flag;
-    if (a.iters) a.iters[e] = r.iters;
-  }
+  write_outputs<64>(P, L, ws, e, ws + L.sol + P.oJ, r, a.upred, a.xpred, a.bw, a.J, a.status, a.iters);
 }
 
 template <class M, int PH>
 hipError_t launch_ph(const SolveLaunch& s, const PhArgs& a, int it, hipStream_t st) {
-  if (s.lds_bytes > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)k_ph<M, PH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)s.lds_bytes);
-    if (e != hipSuccess) return e;
-  }
+  const hipError_t e = optin_lds((const void*)k_ph<M, PH>, s.lds_bytes);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_ph<M, PH>), dim3(a.batch), dim3(64), s.lds_bytes, st, a, it);
   return hipGetLastError();
 }
 
 // the whole IPM of one solve launch (after k_tree on s.stream), host-driven over the iterations.
-// Mode 1 splits the batch into s.nsub sub-batches, each on a stream of its own: a phase kernel
+// Mode 1 splits the batch into s.ph->nsub sub-batches, each on a stream of its own: a phase kernel
 // waits for the slowest ego of its sub-batch, and the other sub-batches' kernels fill the gap
 // (the HIP streams map to separate hardware queues).
 template <class M>
 hipError_t launch_ipm_phased(const SolveLaunch& s) {
   hipError_t e;
-  if (s.ph_mode == 2 || s.ph_mode == 3) {   // one kernel: grouped out-of-line phases / everything inlined
-    const PhArgs a{s.bundle, s.ws, s.upred, s.xpred, s.bw, s.J, s.status, s.iters, s.d_count, 0, s.batch};
-    const void* kf = s.ph_mode == 3 ? (const void*)k_ipm_g<M, true> : (const void*)k_ipm_g<M, false>;
-    if (s.lds_bytes > 64 * 1024 &&
-        (e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds_bytes)) != hipSuccess)
-      return e;
-    if (s.ph_mode == 3) hipLaunchKernelGGL((k_ipm_g<M, true>), dim3(a.batch), dim3(64), s.lds_bytes, s.stream, a);
+  if (s.ph->ph_mode == 2 || s.ph->ph_mode == 3) {   // one kernel: grouped out-of-line phases / everything inlined
+    const PhArgs a{s.bundle, s.ws, s.upred, s.xpred, s.bw, s.J, s.status, s.iters, s.ph->d_count, 0, s.batch};
+    const void* kf = s.ph->ph_mode == 3 ? (const void*)k_ipm_g<M, true> : (const void*)k_ipm_g<M, false>;
+    if ((e = optin_lds(kf, s.lds_bytes)) != hipSuccess) return e;
+    if (s.ph->ph_mode == 3) hipLaunchKernelGGL((k_ipm_g<M, true>), dim3(a.batch), dim3(64), s.lds_bytes, s.stream, a);
     else hipLaunchKernelGGL((k_ipm_g<M, false>), dim3(a.batch), dim3(64), s.lds_bytes, s.stream, a);
     return hipGetLastError();
   }
-  const int ns = s.nsub < 1 ? 1 : s.nsub > kMaxSub ? kMaxSub : s.nsub;
+  const int ns = s.ph->nsub < 1 ? 1 : s.ph->nsub > kMaxSub ? kMaxSub : s.ph->nsub;
   const int per = (s.batch + ns - 1) / ns;
   PhArgs a[kMaxSub];
   hipStream_t st[kMaxSub];
@@ -229,19 +202,19 @@ hipError_t launch_ipm_phased(const SolveLaunch& s) {
   for (int i = 0; i < ns && i * per < s.batch; ++i, ++nsub) {
     const int lo = i * per, hi = lo + per < s.batch ? lo + per : s.batch;
     a[i] = PhArgs{s.bundle, s.ws, s.upred, s.xpred, s.bw, s.J, s.status, s.iters,
-                  s.d_count + (size_t)i * (s.maxit + 1), lo, hi - lo};
-    st[i] = ns == 1 ? s.stream : s.sub[i];
+                  s.ph->d_count + (size_t)i * (s.ph->maxit + 1), lo, hi - lo};
+    st[i] = ns == 1 ? s.stream : s.ph->sub[i];
     live[i] = true;
   }
 #define BMPC_PH(ph, it_, i)                                    \
   if ((e = launch_ph<M, ph>(s, a[i], it_, st[i])) != hipSuccess) \
     return e;
-  if ((e = hipMemsetAsync(s.d_count, 0, sizeof(int32_t) * (size_t)nsub * (s.maxit + 1), s.stream)) != hipSuccess)
+  if ((e = hipMemsetAsync(s.ph->d_count, 0, sizeof(int32_t) * (size_t)nsub * (s.ph->maxit + 1), s.stream)) != hipSuccess)
     return e;
   if (ns > 1) {   // the sub-streams start after k_tree and the counter reset on s.stream
-    if ((e = hipEventRecord(s.sub_ev[kMaxSub], s.stream)) != hipSuccess) return e;
+    if ((e = hipEventRecord(s.ph->sub_ev[kMaxSub], s.stream)) != hipSuccess) return e;
     for (int i = 0; i < nsub; ++i)
-      if ((e = hipStreamWaitEvent(st[i], s.sub_ev[kMaxSub], 0)) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(st[i], s.ph->sub_ev[kMaxSub], 0)) != hipSuccess) return e;
   }
   for (int i = 0; i < nsub; ++i) {
     BMPC_PH(PH_INIT1, 0, i)
@@ -249,13 +222,13 @@ hipError_t launch_ipm_phased(const SolveLaunch& s) {
     BMPC_PH(PH_INIT3, 0, i)
   }
   int next_check = BMPC_PH_FIRST;
-  for (int it = 0; it <= s.maxit; ++it) {
+  for (int it = 0; it <= s.ph->maxit; ++it) {
     bool any = false;
     for (int i = 0; i < nsub; ++i) {
       if (!live[i]) continue;
       any = true;
       BMPC_PH(PH_RES, it, i)
-      if (it == s.maxit) continue;   // RES exits every ego at maxit
+      if (it == s.ph->maxit) continue;   // RES exits every ego at maxit
       BMPC_PH(PH_FAC, it, i)
       BMPC_PH(PH_CPL, it, i)
       BMPC_PH(PH_BKP, it, i)
@@ -267,25 +240,25 @@ hipError_t launch_ipm_phased(const SolveLaunch& s) {
       BMPC_PH(PH_RFC1, it, i)
       BMPC_PH(PH_UPD, it, i)
     }
-    if (!any || it == s.maxit) break;
+    if (!any || it == s.ph->maxit) break;
     if (it + 1 >= next_check) {
       next_check += BMPC_PH_CHECK;
       for (int i = 0; i < nsub; ++i)
-        if (live[i] && (e = hipMemcpyAsync(s.h_count + i, a[i].count + it, sizeof(int32_t), hipMemcpyDeviceToHost,
+        if (live[i] && (e = hipMemcpyAsync(s.ph->h_count + i, a[i].count + it, sizeof(int32_t), hipMemcpyDeviceToHost,
                                            st[i])) != hipSuccess)
           return e;
       for (int i = 0; i < nsub; ++i) {
         if (!live[i]) continue;
         if ((e = hipStreamSynchronize(st[i])) != hipSuccess) return e;
-        if (s.h_count[i] == 0) live[i] = false;   // every ego of the sub-batch has exited
+        if (s.ph->h_count[i] == 0) live[i] = false;   // every ego of the sub-batch has exited
       }
     }
   }
   for (int i = 0; i < nsub; ++i) {
     BMPC_PH(PH_FIN, 0, i)
     if (ns > 1) {   // s.stream resumes after every sub-batch
-      if ((e = hipEventRecord(s.sub_ev[i], st[i])) != hipSuccess) return e;
-      if ((e = hipStreamWaitEvent(s.stream, s.sub_ev[i], 0)) != hipSuccess) return e;
+      if ((e = hipEventRecord(s.ph->sub_ev[i], st[i])) != hipSuccess) return e;
+      if ((e = hipStreamWaitEvent(s.stream, s.ph->sub_ev[i], 0)) != hipSuccess) return e;
     }
   }
 #undef BMPC_PH

@@ -1,7 +1,9 @@
 """The fused closed loop (bmpc_loop_device, k_loop): K steps of every ego in one launch give the
 same bits as K rounds of bmpc_env_step + bmpc_solve_device (k_env, k_tree, k_ipm launched per
 step) -- the scene, the plan's last outputs, the statistics and the warm start carried between
-calls -- and a loop split over several calls is the same loop."""
+calls -- and a loop split over several calls is the same loop.  Both instantiations of k_loop are
+held to it: the LDS-rich one the executor chooses for these shapes and the lean one
+(BMPC_LDS_RICH=0), the latter also at a shape whose coupling system takes the wave LU on the slab."""
 import numpy as np
 import pytest
 
@@ -13,14 +15,17 @@ pytestmark = pytest.mark.gpu
 B = 300   # more egos than CUs: the batch takes the one-wave k_ipm, so the loop is fused
 
 
-def _run(torch, chunks, monkeypatch, fused_env=None):
+def _run(torch, chunks, monkeypatch, fused_env=None, lds_rich=None, N=20, NB=1):
+    """lds_rich: BMPC_LDS_RICH for the run (None: unset, the executor chooses)."""
     from bmpc import plan
     for k in ("BMPC_BLOCK_EGOS", "BMPC_LDS_RICH", "BMPC_LOOP_FUSED"):
         monkeypatch.delenv(k, raising=False)
     if fused_env is not None:
         monkeypatch.setenv("BMPC_LOOP_FUSED", fused_env)
+    if lds_rich is not None:
+        monkeypatch.setenv("BMPC_LDS_RICH", lds_rich)
     x, z, xref, tgt = seeded_batch(B, seed=5)
-    pl = plan.BatchPlan(highway_desc(N=20, NB=1), B)
+    pl = plan.BatchPlan(highway_desc(N=N, NB=NB), B)
     pl.set_policies(highway_policy_rows(tgt))
     dev = torch.device("cuda", 0)
     f64 = dict(dtype=torch.float64, device=dev)
@@ -67,24 +72,45 @@ def _same(a, b):
             assert np.array_equal(a[k], b[k]), k
 
 
-def test_fused_loop_equals_per_step_launches(monkeypatch):
+# (BMPC_LDS_RICH, the per-step solver kernel, the fused kernel)
+RICH = (None, abi.KERNEL_IPM_RICH, abi.KERNEL_LOOP_RICH)   # the executor's own choice at these shapes
+LEAN = ("0", abi.KERNEL_IPM_LEAN, abi.KERNEL_LOOP_LEAN)
+
+
+@pytest.mark.parametrize("lds_rich,k_step,k_loop", [RICH, LEAN], ids=["rich", "lean"])
+def test_fused_loop_equals_per_step_launches(monkeypatch, lds_rich, k_step, k_loop):
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
-    ref, kr = _run(torch, ["step"] * 5, monkeypatch)
-    assert set(kr) == {abi.KERNEL_IPM_RICH}, kr
-    fused, kf = _run(torch, [5], monkeypatch)
-    assert kf == [abi.KERNEL_LOOP_RICH], kf
+    ref, kr = _run(torch, ["step"] * 5, monkeypatch, lds_rich=lds_rich)
+    assert set(kr) == {k_step}, kr
+    fused, kf = _run(torch, [5], monkeypatch, lds_rich=lds_rich)
+    assert kf == [k_loop], kf
     _same(ref, fused)
-    split, ks = _run(torch, [2, 3], monkeypatch)          # a loop continued over calls
-    assert ks == [abi.KERNEL_LOOP_RICH] * 2, ks
+    split, ks = _run(torch, [2, 3], monkeypatch, lds_rich=lds_rich)          # a loop continued over calls
+    assert ks == [k_loop] * 2, ks
     _same(ref, split)
-    mixed, _ = _run(torch, ["step", 4], monkeypatch)        # t0 > 0 after a per-step start
+    mixed, _ = _run(torch, ["step", 4], monkeypatch, lds_rich=lds_rich)        # t0 > 0 after a per-step start
     _same(ref, mixed)
-    steps, kp = _run(torch, [5], monkeypatch, fused_env="0")   # the per-step path of the same call
-    assert kp == [abi.KERNEL_IPM_RICH], kp
+    steps, kp = _run(torch, [5], monkeypatch, fused_env="0", lds_rich=lds_rich)   # the per-step path of the same call
+    assert kp == [k_step], kp
     _same(ref, steps)
     assert np.all(ref["st"] >= 0) and ref["stats"][:, abi.ENVS_SOLVES].min() == 4
+
+
+def test_lean_fused_loop_with_wave_lu_equals_per_step_launches(monkeypatch):
+    """N=8, NB=2: the coupling system's order reaches BMPC_WAVE_LU_MIN1, so the lean launches
+    factor it with small_lu_wave on the slab.  Every ego solves (no equality between failures)."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    lds_rich, k_step, k_loop = LEAN
+    ref, kr = _run(torch, ["step"] * 3, monkeypatch, lds_rich=lds_rich, N=8, NB=2)
+    assert set(kr) == {k_step}, kr
+    fused, kf = _run(torch, [3], monkeypatch, lds_rich=lds_rich, N=8, NB=2)
+    assert kf == [k_loop], kf
+    _same(ref, fused)
+    assert np.all(ref["st"] >= 0), np.unique(ref["st"], return_counts=True)
 
 
 def test_loop_rejects_other_plans():
