@@ -37,7 +37,7 @@ def sources():
     solver kernels (compiled in parallel), the host-side plan builders."""
     srcs = [os.path.join(CSRC, f) for f in ("bmpc_hip.hip", "bmpc_k_highway.hip", "bmpc_k_highway_t.hip",
                                             "bmpc_k_merge.hip", "bmpc_k_merge_loop.hip", "bmpc_k_quadruped.hip",
-                                            "bmpc_kb_highway.hip",
+                                            "bmpc_k_quad_loop.hip", "bmpc_kb_highway.hip",
                                             "bmpc_kb_highway_t.hip", "bmpc_kb_merge.hip", "bmpc_kb_quadruped.hip",
                                             "bmpc_plan.cpp", "bmpc_qpplan.cpp")]
     if _phased():
@@ -128,6 +128,8 @@ _SIGS = {
     "bmpc_set_merge_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3),
     "bmpc_merge_env_step": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 10),
     "bmpc_merge_loop_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "bmpc_quad_env_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 10),
+    "bmpc_quad_loop_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10),
     "bmpc_qp_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
                       + [C.c_int, C.c_double] + [C.c_void_p] * 5),
 }

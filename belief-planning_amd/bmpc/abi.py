@@ -90,6 +90,23 @@ def make_merge_env(n_lane=2, merge_lane=1, merge_s=50.0, W=2.5, Kpsi=0.1, v0=20.
     return E
 
 
+# quadruped scene: three-component states in the slots before ENV_COLL (bmpc_env_quad.h)
+QENV_X, QENV_Z, QENV_UOBS, QENV_XDES = 0, 3, 6, 9
+
+
+class QuadEnvDesc(C.Structure):
+    """bmpc_quad_env_desc: the main_quadruped scene's literals (quadruped_env.py:98-110)."""
+    _fields_ = [("switch_clearance", C.c_double), ("lookahead", C.c_double), ("near", C.c_double)]
+
+
+def make_quad_env(switch_clearance=0.5, lookahead=5.0, near=0.1):
+    """Scene constants of quadruped_env.Quad_env.step: the obstacle keeps backup 0 above 0.5 m of
+    clearance (:98), x_ref lies 5 m ahead (:108), the ego's own heading within 0.1 m of x_des (:110)."""
+    E = QuadEnvDesc()
+    E.switch_clearance, E.lookahead, E.near = switch_clearance, lookahead, near
+    return E
+
+
 def _fill(arr, values):
     v = np.asarray(values, dtype=np.float64).ravel()
     for i, x in enumerate(v):

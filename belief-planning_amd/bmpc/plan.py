@@ -138,6 +138,25 @@ class BatchPlan:
                                                      iters_ptr, stats_ptr, stream)]
         check(lib().bmpc_merge_loop_device(self._h, int(t0), int(nsteps), *vp), "bmpc_merge_loop_device")
 
+    def quad_env_step_device(self, env: abi.QuadEnvDesc, t: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr,
+                             J_ptr=None, status_ptr=None, iters_ptr=None, stats_ptr=None, stream=None):
+        """One closed-loop main_quadruped step of every ego on the device (bmpc_quad_env_step): Euler
+        steps of both robots, the obstacle's backup choice from the clearance along the ego's
+        predicted path, x_ref towards the scene's per-ego x_des -> the next solve's x, z, xref
+        [batch][3].  QUADRUPED plans with an OSQP-class controller.  Async."""
+        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr,
+                                                     x_ptr, z_ptr, xref_ptr, stats_ptr, stream)]
+        check(lib().bmpc_quad_env_step(self._h, C.byref(env), int(t), *vp), "bmpc_quad_env_step")
+
+    def quad_loop_device(self, env: abi.QuadEnvDesc, t0: int, nsteps: int, scene_ptr, upred_ptr, x_ptr, z_ptr,
+                         xref_ptr, J_ptr, status_ptr, iters_ptr, stats_ptr=None, stream=None):
+        """nsteps closed-loop main_quadruped steps of every ego (bmpc_quad_loop_device):
+        quad_env_step_device(t) then solve_device per step, the same results; one fused launch
+        (k_loop with the QP solver) unless BMPC_LOOP_FUSED=0.  Async on `stream`."""
+        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
+                                                     iters_ptr, stats_ptr, stream)]
+        check(lib().bmpc_quad_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_quad_loop_device")
+
     def get_transform(self):
         """The S [B,n,n], bx [B,nFx] and (S on, bx set) flags [B,2] in the egos' transform slots."""
         B, n, nF = self.batch, self.desc.n, self.desc.nFx

@@ -175,6 +175,57 @@ def seeded_quadruped_batch(B, seed=1):
     return x, z, quadruped_xref(x)
 
 
+QUAD_X_DES = np.array([5.0, -3.0, 0.0])   # quadruped_env.sim's goal (:327)
+
+
+def seeded_quadruped_goals(B, seed=1):
+    """Per-ego goals of a quadruped population: row 0 is sim's x_des, the others lie 2 m around it
+    with any heading."""
+    rng = np.random.default_rng([seed, 1])
+    g = QUAD_X_DES + np.stack([rng.uniform(-2, 2, B), rng.uniform(-2, 2, B), rng.uniform(-np.pi, np.pi, B)], 1)
+    g[0] = QUAD_X_DES
+    return g
+
+
+def quad_scene(x, z, x_des):
+    """The quadruped scene's initial state rows [B, ENV_STRIDE] (csrc/bmpc_env_quad.h)."""
+    x = np.atleast_2d(np.asarray(x, float))
+    scene = np.zeros((x.shape[0], abi.ENV_STRIDE))
+    scene[:, abi.QENV_X:abi.QENV_X + 3] = x
+    scene[:, abi.QENV_Z:abi.QENV_Z + 3] = np.atleast_2d(np.asarray(z, float))
+    scene[:, abi.QENV_XDES:abi.QENV_XDES + 3] = np.asarray(x_des, float)
+    return scene
+
+
+def quadruped_population(B, steps, seed=0, device=0):
+    """`steps` closed-loop main_quadruped steps of B seeded episodes (seeded_quadruped_batch, each
+    ego walking to a goal of its own), resident on the GPU (BatchPlan.quad_loop_device).  Returns
+    the per-ego statistics rows [B, ENV_NSTAT] (the form distributed.episode_stats takes; a step's
+    solve is booked by the next step, so they cover steps - 1 solves) and the final scene
+    [B, ENV_STRIDE]."""
+    import torch
+    from . import plan
+    x, z, _ = seeded_quadruped_batch(B, seed)
+    pl = plan.BatchPlan(quadruped_desc(), B, device)
+    pl.set_policies(quadruped_policy_rows(B))
+    dev = torch.device("cuda", device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    scene = torch.tensor(quad_scene(x, z, seeded_quadruped_goals(B, seed)), **f64)
+    up = torch.zeros((B, pl.U, 3), **f64)
+    J = torch.zeros(B, **f64)
+    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
+    tx, tz, tr = (torch.zeros((B, 3), **f64) for _ in range(3))
+    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
+    stream = torch.cuda.Stream(dev)
+    pl.quad_loop_device(abi.make_quad_env(), 0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(),
+                        tr.data_ptr(), J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    out = stats.cpu().numpy(), scene.cpu().numpy()
+    pl.close()
+    return out
+
+
 def quadruped_xref(x, x_des=(5.0, -3.0, 0.0)):
     """Reference of the recorded quadruped loop (tools/gen_golden.py, after quadruped_env.py):
     a point at most 5 m towards x_des, heading along the way."""

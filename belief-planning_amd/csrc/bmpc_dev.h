@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "bmpc_env_merge.h"
+#include "bmpc_env_quad.h"
 #include "bmpc_hmm.h"
 #include "bmpc_plan.h"
 #include "bmpc_qp.h"
@@ -430,16 +431,36 @@ __device__ __attribute__((noinline)) void loop_merge_env_step(const bmpc_merge_e
   merge_env_step_slab(env, R, P, L, t, st, ws, up, x, z, xr);
 }
 
+// The quadruped loop's solve and scene step as calls (OSQP-class controllers: env_accumulate reads
+// their status, 1 = solved).
+template <class X, class M>
+__device__ __attribute__((noinline)) IpmResult loop_qp(const X ex, const Plan& P, const Layout& L, EgoView E) {
+  return solve_ego_qp<X, M>(ex, P, L, E);
+}
+__device__ __attribute__((noinline)) void loop_quad_env_step(const bmpc_quad_env_desc& env, const Plan& P, int t,
+                                                             double* st, const bmpc_policy* pol, const double* up,
+                                                             double* x, double* z, double* xr, double Jv, int status,
+                                                             int iters, double* stats) {
+  if (t > 0 && stats) env_accumulate(st, Jv, status, iters, false, stats);
+  quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr);
+}
+
 #ifndef BMPC_MERGE_LOOP_INLINE_IPM
 #define BMPC_MERGE_LOOP_INLINE_IPM 1
 #endif
+#ifndef BMPC_QUAD_LOOP_INLINE_QP
+#define BMPC_QUAD_LOOP_INLINE_QP 1
+#endif
 // The scene of a k_loop (its kernel argument): one ego's scene step on lane 0, through an
 // out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
-// ego's transform slots.  kInlineIpm: the IPM inlined into the kernel as k_ipm has it (the tree
-// and scene steps stay calls) instead of a call of its own -- as a callee the IPM's frame grows
-// from k_ipm's ~590 to ~1,490 bytes per lane (merge loop: 2,528 bytes of scratch against 1,648;
-// DESIGN §5c).  The overtake loop keeps the form it was measured in (§5b).
+// ego's transform slots, the quadruped scene neither.  kQp: the step's solve is the OSQP-class
+// controllers' solve_ego_qp (k_qp's) instead of the CVaR IPM.  kInlineIpm: the solve inlined into
+// the kernel as k_ipm / k_qp have it (the tree and scene steps stay calls) instead of a call of
+// its own -- as a callee the IPM's frame grows from k_ipm's ~590 to ~1,490 bytes per lane (merge
+// loop: 2,528 bytes of scratch against 1,648), the QP's loop from 1,152 to 1,280
+// (§5d).  The overtake loop keeps the form it was measured in (§5b).
 struct OvertakeScene {
+  static constexpr bool kQp = false;
   static constexpr bool kInlineIpm = false;
   bmpc_env_desc env;
   __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
@@ -448,6 +469,7 @@ struct OvertakeScene {
   }
 };
 struct MergeScene {
+  static constexpr bool kQp = false;
   static constexpr bool kInlineIpm = BMPC_MERGE_LOOP_INLINE_IPM != 0;
   bmpc_merge_env_desc env;
   MergeRef ref;
@@ -456,9 +478,19 @@ struct MergeScene {
     loop_merge_env_step(env, ref, P, L, t, st, ws, up, x, z, xr, Jv, status, iters, stats);
   }
 };
+struct QuadScene {
+  static constexpr bool kQp = true;
+  static constexpr bool kInlineIpm = BMPC_QUAD_LOOP_INLINE_QP != 0;   // (both forms measured)
+  bmpc_quad_env_desc env;
+  __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
+                       double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
+    loop_quad_env_step(env, P, t, st, pe, up, x, z, xr, Jv, status, iters, stats);
+  }
+};
 
-// nsteps closed-loop steps of one ego per wave (bmpc_loop_device, bmpc_merge_loop_device): the
-// scene step of k_env / k_env_merge (lane 0), k_tree's tree step and k_ipm's solve + unpack, in
+// nsteps closed-loop steps of one ego per wave (bmpc_loop_device, bmpc_merge_loop_device,
+// bmpc_quad_loop_device): the scene step of k_env / k_env_merge / k_env_quad (lane 0), k_tree's tree
+// step and k_ipm's (SC::kQp: k_qp's) solve + unpack, in
 // that order, per step -- the same per-ego functions the three launches run, so the same bits --
 // with no device-wide boundary between the steps: the egos' loops are independent, and a wave
 // whose ego needs few IPM iterations in one step starts its next step instead of idling until the
@@ -473,7 +505,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const Plan& P = B->P;
   const Layout& L = B->L;
   extern __shared__ double lds_dyn[];
-  const auto ex = solver_exec<M::kTransform, TL>(P, lds_dyn);
+  constexpr bool TR = SC::kQp ? false : M::kTransform;   // (k_qp's executor takes no transform)
+  const auto ex = solver_exec<TR, TL>(P, lds_dyn);
   bmpc_policy* pe = pol + (size_t)e * P.m;
   EgoView E{ws + L.stride * (size_t)e, pe};
   double* st = scene + (size_t)e * ENV_STRIDE;
@@ -488,15 +521,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
       sc.step(P, L, t, st, pe, E.ws, up, x, z, xr, J[e], status[e], iters[e],
               stats ? stats + (size_t)e * ENVS_STRIDE : nullptr);
     __syncthreads();
-    using X = DevExecT<M::kTransform, TL>;
+    using X = DevExecT<TR, TL>;
     loop_tree_step<X, M>(ex, P, L, E, x, z, xr);   // k_tree
-    IpmResult r;   // k_ipm
-    if constexpr (SC::kInlineIpm) r = solve_ego_ipm<X, M>(ex, P, L, E);
-    else r = loop_ipm<X, M>(ex, P, L, E);
+    IpmResult r;   // k_ipm / k_qp
+    if constexpr (SC::kQp) {
+      if constexpr (SC::kInlineIpm) r = solve_ego_qp<X, M>(ex, P, L, E);
+      else r = loop_qp<X, M>(ex, P, L, E);
+    } else {
+      if constexpr (SC::kInlineIpm) r = solve_ego_ipm<X, M>(ex, P, L, E);
+      else r = loop_ipm<X, M>(ex, P, L, E);
+    }
     const double* w = E.ws;
     for (int i = lane; i < P.U * P.d; i += 64) up[i] = w[L.upred + i];
     if (lane == 0) {
-      J[e] = w[L.sol + P.oJ];
+      if constexpr (SC::kQp) J[e] = r.pcost;
+      else J[e] = w[L.sol + P.oJ];
       status[e] = r.exit_flag;
       iters[e] = r.iters;
     }
@@ -626,11 +665,13 @@ LaunchFn launch_tree_highway, launch_solver_highway, launch_solver_blk_highway;
 LaunchFn launch_tree_highway_t, launch_solver_highway_t, launch_solver_blk_highway_t;
 LaunchFn launch_tree_merge, launch_solver_merge, launch_solver_blk_merge;
 LaunchFn launch_tree_quadruped, launch_solver_quadruped, launch_solver_blk_quadruped;
-// the fused closed loops (bmpc_k_highway.hip, bmpc_k_merge_loop.hip)
+// the fused closed loops (bmpc_k_highway.hip, bmpc_k_merge_loop.hip, bmpc_k_quad_loop.hip)
 hipError_t launch_loop_highway(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
                                double* stats);
 hipError_t launch_loop_merge(const SolveLaunch& a, const bmpc_merge_env_desc& env, const MergeRef& ref, int t0,
                              int nsteps, double* scene, double* stats);
+hipError_t launch_loop_quad(const SolveLaunch& a, const bmpc_quad_env_desc& env, int t0, int nsteps, double* scene,
+                            double* stats);
 
 #if defined(BMPC_WITH_PHASED)
 // The phase-per-kernel CVaR IPM (experimental/bmpc_dev_ph.h, bmpc_kp_*.hip; tools-only builds with

@@ -64,6 +64,22 @@ __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E,
                       x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4);
 }
 
+// one thread per ego: the quadruped scene step (bmpc_env_quad.h) around the solve of an OSQP-class
+// controller (status 1 = solved)
+__global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, int t, int batch, double* scene,
+                           const bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
+                           const int32_t* iters, double* x, double* z, double* xref, double* stats) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= batch) return;
+  const Plan& P = B->P;
+  double* st = scene + (size_t)e * ENV_STRIDE;
+  if (t > 0 && stats && J && status && iters)
+    env_accumulate(st, J[e], status[e], iters[e], false, stats + (size_t)e * ENVS_STRIDE);
+  quad_env_step_ego(E, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol + (size_t)e * P.m,
+                    upred ? upred + (size_t)e * P.U * P.d : nullptr, x + (size_t)e * 3, z + (size_t)e * 3,
+                    xref + (size_t)e * 3);
+}
+
 __global__ void k_gather(const double* __restrict__ ws, size_t stride, size_t off, int count,
                          double* __restrict__ out, int batch) {
   const size_t tot = (size_t)batch * count;
@@ -671,8 +687,10 @@ struct LaunchChoice {
 // takes this path (default: one ego per CU; 0 disables it); BMPC_BLOCK_WAVES: 4 or 8;
 // BMPC_BLK_LDS=0: the small-batch kernel keeps every array in the slab.
 // Larger CVaR batches may fuse a closed loop into one launch, unless a policy tracks the lane
-// reference or BMPC_LOOP_FUSED=0 asks for the per-step launches (A/B).
-static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform) {
+// reference or BMPC_LOOP_FUSED=0 asks for the per-step launches (A/B).  qp_loop: the caller is the
+// quadruped loop, whose k_loop runs the QP solver -- its OSQP-class plans fuse too (no other loop
+// has a k_loop for them: robust overtake plans keep their launches per step).
+static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform, bool qp_loop = false) {
   const Plan& P = pl->hp.plan;
   const bmpc_ctx* c = pl->ctx;
   const bool cvar = P.desc.controller == BMPC_CTRL_CVAR;
@@ -697,7 +715,7 @@ static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform) {
     if (want > ch.lds_bytes && want <= c->lds_per_cu) ch.lds_bytes = want;
   }
   const char* ef = getenv("BMPC_LOOP_FUSED");
-  ch.fused_loop = cvar && !pl->psiref && !(ef && atoi(ef) == 0);
+  ch.fused_loop = (cvar || qp_loop) && !pl->psiref && !(ef && atoi(ef) == 0);
   return ch;
 }
 
@@ -768,14 +786,15 @@ static int launch_solve(bmpc_plan* pl, const double* d_x, const double* d_z, con
 extern "C++" {
 // nsteps closed-loop steps of a scene (bmpc_loop_device, bmpc_merge_loop_device): one k_loop launch
 // (`fused`) for batches that choose_launch lets fuse, otherwise the scene's step (`step`) + the
-// solve launches per step -- same results either way.  retargets: the scene's step rewrites d_pol.
+// solve launches per step -- same results either way.  retargets: the scene's step rewrites d_pol;
+// qp_loop: the scene's k_loop runs the QP solver (choose_launch).
 template <class Step, class Fused>
-static int run_loop(bmpc_plan* pl, bool retargets, int t0, int nsteps, double* d_upred, double* d_x, double* d_z,
+static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_upred, double* d_x, double* d_z,
                     double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters, void* stream, Step step,
                     Fused fused) {
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
-  const LaunchChoice ch = choose_launch(pl, plan_takes_transform(pl->hp.plan));
+  const LaunchChoice ch = choose_launch(pl, plan_takes_transform(pl->hp.plan), qp_loop);
   if (!ch.fused_loop) {
     for (int k = 0; k < nsteps; ++k) {
       if (int rc = step(t0 + k)) return rc;
@@ -866,7 +885,7 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_loop_device: nsteps >= 1 and t0 >= 0");
   if (env->n_lane < 1) return fail(-22, "bmpc_loop_device: n_lane < 1");
   return run_loop(
-      pl, true, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, true, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
       },
@@ -924,13 +943,52 @@ int bmpc_merge_loop_device(bmpc_plan* pl, int t0, int nsteps, double* d_scene, d
   if (!pl->n_mref) return fail(-22, "bmpc_merge_loop_device: no merge scene (bmpc_set_merge_scene)");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_merge_loop_device: nsteps >= 1 and t0 >= 0");
   return run_loop(
-      pl, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, false, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_merge_env_step(pl, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
       },
       [&](const SolveLaunch& a) {
         return launch_loop_merge(a, pl->menv, MergeRef{pl->d_mref, pl->n_mref}, t0, nsteps, d_scene, d_stats);
       });
+}
+
+// "" for the plans the quadruped scene runs on
+static std::string check_quad_scene_plan(const Plan& P) {
+  if (P.desc.model != BMPC_MODEL_QUADRUPED || P.n != 3 || P.d != 3 || P.desc.controller == BMPC_CTRL_CVAR)
+    return "the quadruped scene needs a QUADRUPED plan (n = d = 3) with an OSQP-class controller";
+  return "";
+}
+
+int bmpc_quad_env_step(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t, double* d_scene, const double* d_upred,
+                       const double* d_J, const int32_t* d_status, const int32_t* d_iters, double* d_x, double* d_z,
+                       double* d_xref, double* d_stats, void* stream) {
+  if (!pl || !env || !d_scene || !d_x || !d_z || !d_xref) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (const std::string e = check_quad_scene_plan(P); !e.empty()) return fail(-22, "bmpc_quad_env_step: " + e);
+  if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_quad_env_step: t >= 0, and t > 0 needs the last uPred");
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  hipStream_t s = plan_stream(pl, stream);
+  hipLaunchKernelGGL(k_env_quad, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, *env, t, pl->batch, d_scene,
+                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int bmpc_quad_loop_device(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t0, int nsteps, double* d_scene,
+                          double* d_upred, double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status,
+                          int32_t* d_iters, double* d_stats, void* stream) {
+  if (!pl || !env || !d_scene || !d_upred || !d_x || !d_z || !d_xref || !d_J || !d_status || !d_iters)
+    return fail(-22, "null argument");
+  if (const std::string e = check_quad_scene_plan(pl->hp.plan); !e.empty())
+    return fail(-22, "bmpc_quad_loop_device: " + e);
+  if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_quad_loop_device: nsteps >= 1 and t0 >= 0");
+  return run_loop(
+      pl, false, true, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      [&](int t) {
+        return bmpc_quad_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats,
+                                  stream);
+      },
+      [&](const SolveLaunch& a) { return launch_loop_quad(a, *env, t0, nsteps, d_scene, d_stats); });
 }
 
 static int gather(bmpc_plan* pl, size_t off, int count, double* host) {

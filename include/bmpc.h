@@ -31,6 +31,7 @@
  *                                                          Highway_env_branch.py:83-184,421-429
  *   bmpc_merge_env_step<- Highway_env_merge.step + the same collision rule
  *                                                          Highway_env_branch.py:317-380,421-429
+ *   bmpc_quad_env_step <- Quad_env.step                    quadruped_env.py:67-130
  *
  * Conventions: all host buffers are caller-owned, C-contiguous, ego-major, float64
  * (int32 for status/iteration counts).  Return codes are 0 on success and a negative
@@ -173,7 +174,7 @@ enum {
   BMPC_KERNEL_IPM_BLK8 = 4,  /* k_solve_blk, one ego per 8-wave workgroup (small batches)  */
   BMPC_KERNEL_QP_RICH = 5,   /* k_qp (OSQP-class controllers), LDS-rich                    */
   BMPC_KERNEL_QP_LEAN = 6,   /* k_qp, lean                                                 */
-  BMPC_KERNEL_LOOP_RICH = 7, /* k_loop (bmpc_loop_device): env + tree + IPM steps per ego    */
+  BMPC_KERNEL_LOOP_RICH = 7, /* k_loop (bmpc_*loop_device): env + tree + IPM / QP steps per ego */
   BMPC_KERNEL_LOOP_LEAN = 8  /* k_loop, lean                                                 */
 };
 
@@ -387,6 +388,34 @@ int bmpc_merge_env_step(bmpc_plan* plan, int t, double* d_scene, const double* d
 int bmpc_merge_loop_device(bmpc_plan* plan, int t0, int nsteps, double* d_scene, double* d_upred,
                            double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status,
                            int32_t* d_iters, double* d_stats, void* stream);
+
+/* Closed-loop main_quadruped scene on the device, one scene per ego of a QUADRUPED plan with an
+ * OSQP-class controller: replaces quadruped_env.Quad_env.step (quadruped_env.py:67-130) around the
+ * solve.  The robots' lengths and col_tol come from the plan's model constants (mc). */
+typedef struct {
+  double switch_clearance; /* the obstacle keeps backup 0 while its clearance exceeds this: 0.5 (:98) */
+  double lookahead;        /* x_ref lies at most this far towards x_des: 5 m (:108)                     */
+  double near;             /* within this distance of x_des the heading reference is the ego's own: 0.1 (:110) */
+} bmpc_quad_env_desc;
+
+/* One closed-loop quadruped step t of every ego: bmpc_env_step's arguments with x, z, xref
+ * [batch][3].  scene [batch][BMPC_ENV_STRIDE]: ego x[0..2], obstacle z[3..5], the obstacle's input
+ * [6..8], the ego's goal x_des[9..11] (written by the caller with x and z; the scene never changes
+ * it), slots 12-14 as bmpc_env_step's -- the reference has no collision rule for this scene, so
+ * slot 12 and the statistics' collision columns stay 0 --, the rest zero at t = 0.  QUADRUPED plans
+ * with n = d = 3 and an OSQP-class controller (not CVaR); -22 otherwise. */
+int bmpc_quad_env_step(bmpc_plan* plan, const bmpc_quad_env_desc* env, int t, double* d_scene,
+                       const double* d_upred, const double* d_J, const int32_t* d_status,
+                       const int32_t* d_iters, double* d_x, double* d_z, double* d_xref, double* d_stats,
+                       void* stream);
+
+/* nsteps closed-loop quadruped steps: bmpc_loop_device's arguments and contract
+ * (bmpc_quad_env_step(t) then bmpc_solve_device per step, bit for bit) -- ONE k_loop launch running
+ * the QP solver per step (BMPC_KERNEL_LOOP_RICH / _LEAN) unless BMPC_LOOP_FUSED=0 asks for the
+ * launches per step (BMPC_KERNEL_QP_RICH / _LEAN).  The same plans as bmpc_quad_env_step. */
+int bmpc_quad_loop_device(bmpc_plan* plan, const bmpc_quad_env_desc* env, int t0, int nsteps,
+                          double* d_scene, double* d_upred, double* d_x, double* d_z, double* d_xref,
+                          double* d_J, int32_t* d_status, int32_t* d_iters, double* d_stats, void* stream);
 
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of
