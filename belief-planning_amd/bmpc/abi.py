@@ -107,6 +107,15 @@ def make_quad_env(switch_clearance=0.5, lookahead=5.0, near=0.1):
     return E
 
 
+class LoopRecord(C.Structure):
+    """bmpc_loop_record: the closed loops' per-step recorder (device pointers, ego-major; row r of
+    an ego holds closed-loop step t_base + r).  The last four columns are optional (NULL skips)."""
+    _fields_ = [("capacity", C.c_int32), ("t_base", C.c_int32),
+                ("scene", C.c_void_p), ("xref", C.c_void_p), ("u", C.c_void_p), ("J", C.c_void_p),
+                ("status", C.c_void_p), ("iters", C.c_void_p),
+                ("upred", C.c_void_p), ("xpred", C.c_void_p), ("zpred", C.c_void_p), ("branch_w", C.c_void_p)]
+
+
 def _fill(arr, values):
     v = np.asarray(values, dtype=np.float64).ravel()
     for i, x in enumerate(v):

@@ -24,6 +24,108 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+SCENE_KINDS = {abi.MODEL_HIGHWAY: "overtake", abi.MODEL_HIGHWAY_MERGE: "merge", abi.MODEL_QUADRUPED: "quadruped"}
+
+
+class LoopRecording:
+    """The per-step record of a plan's closed loops (bmpc_loop_record): its columns and the struct
+    that points at them.
+
+    ``cols`` maps the column names of the struct -- scene [B, capacity, ENV_STRIDE], xref
+    [B, capacity, n], u [B, capacity, d], J / status / iters [B, capacity] and, with predictions,
+    upred [B, capacity, U, d], xpred / zpred [B, capacity, T, n], branch_w [B, capacity,
+    nbranch-1] -- to torch tensors on the plan's device (BatchPlan.new_loop_record) or NumPy
+    arrays.  Row r of an ego holds closed-loop step ``t_base + r`` in the device scene's own
+    convention: the scene row as step t's solve saw it (state and inputs OF step t) and that
+    solve's outputs; ``u[:, r]`` is the input the ego applies next.  Highway_sim's post-step
+    ``state_rec[t]`` is therefore ``x[:, t + 1]``; no final post-step row exists.
+
+    ``col(name)`` is the column on the host (a copy when it lives on the device); the properties
+    below are NumPy views of the scene column by scene kind ("overtake", "merge", "quadruped"),
+    through the abi.ENV_* / abi.QENV_* slots.  ``host()`` snapshots every column once.
+
+    Memory: a row is 16 + n + d + 2 doubles (0.2 KB; 8-byte J, 4-byte status and iters), and with
+    predictions U d + 2 T n + nbranch - 1 doubles more: about 5 KB per ego-step at N = 20, NB = 1
+    (T = 64, U = 61: 637 doubles), so 4,096 egos x 20 steps take 0.4 GB with predictions and 16 MB without."""
+
+    CORE = ("scene", "xref", "u", "J", "status", "iters")
+    OPTIONAL = ("upred", "xpred", "zpred", "branch_w")
+
+    def __init__(self, kind, capacity, t_base, cols):
+        if kind not in SCENE_KINDS.values():
+            raise ValueError(f"scene kind {kind!r}: one of {sorted(SCENE_KINDS.values())}")
+        missing = [k for k in self.CORE if cols.get(k) is None]
+        if missing:
+            raise ValueError(f"core columns missing: {missing}")
+        self.kind, self.capacity, self.t_base = kind, int(capacity), int(t_base)
+        self.cols = {k: cols[k] for k in self.CORE + self.OPTIONAL if cols.get(k) is not None}
+        self.struct = None
+        if all(hasattr(v, "data_ptr") for v in self.cols.values()):
+            self.struct = abi.LoopRecord(capacity=self.capacity, t_base=self.t_base,
+                                         **{k: v.data_ptr() for k, v in self.cols.items()})
+
+    @property
+    def nbytes(self):
+        return sum(int(np.prod(v.shape)) * (4 if k in ("status", "iters") else 8) for k, v in self.cols.items())
+
+    def col(self, name):
+        v = self.cols[name]
+        return v if isinstance(v, np.ndarray) else v.cpu().numpy()
+
+    def host(self):
+        """A snapshot with every column on the host (wait for the loop's stream first)."""
+        return LoopRecording(self.kind, self.capacity, self.t_base, {k: self.col(k) for k in self.cols})
+
+    def _scene(self, lo, width=None, kinds=None):
+        if kinds is not None and self.kind not in kinds:
+            raise AttributeError(f"the {self.kind} scene has no such column")
+        s = self.col("scene")
+        return s[..., lo] if width is None else s[..., lo:lo + width]
+
+    @property
+    def _quad(self):
+        return self.kind == "quadruped"
+
+    @property
+    def x(self):
+        """Ego state of each recorded step [B, capacity, n]."""
+        return self._scene(abi.QENV_X, 3) if self._quad else self._scene(abi.ENV_X, 4)
+
+    @property
+    def z(self):
+        """Obstacle state [B, capacity, n]."""
+        return self._scene(abi.QENV_Z, 3) if self._quad else self._scene(abi.ENV_Z, 4)
+
+    @property
+    def u_obs(self):
+        """The obstacle's input chosen at the step (applied by the next step's Euler step)."""
+        return self._scene(abi.QENV_UOBS, 3) if self._quad else self._scene(abi.ENV_UOBS, 2)
+
+    @property
+    def obs_policy(self):
+        """The obstacle's backup choice (Highway_sim's backup_choice_rec)."""
+        return self._scene(abi.ENV_OBSPOL)
+
+    @property
+    def collided(self):
+        return self._scene(abi.ENV_COLL)
+
+    @property
+    def steps(self):
+        """Control steps taken, t + 1 in the row of step t."""
+        return self._scene(abi.ENV_STEPS)
+
+    @property
+    def merged(self):
+        """Merge scene: the ego has left the ramp."""
+        return self._scene(abi.ENV_MERGED, kinds=("merge",))
+
+    @property
+    def x_des(self):
+        """Quadruped scene: the ego's goal."""
+        return self._scene(abi.QENV_XDES, 3, kinds=("quadruped",))
+
+
 class BatchPlan:
     """A batch of ``batch`` independent egos, each with its own scenario tree, warm start
     and policy set, solved together by one kernel launch per phase."""
@@ -36,6 +138,7 @@ class BatchPlan:
         h = C.c_void_p()
         check(lib().bmpc_plan_create(self._ctx, C.byref(desc), self.batch, C.byref(h)), "bmpc_plan_create")
         self._h = h
+        self._loop_record = None   # the attached LoopRecording (set_loop_record)
         info = np.zeros(abi.INFO_COUNT, np.int32)
         check(lib().bmpc_plan_info(h, _p(info)), "bmpc_plan_info")
         self.info = info
@@ -156,6 +259,41 @@ class BatchPlan:
         vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
                                                      iters_ptr, stats_ptr, stream)]
         check(lib().bmpc_quad_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_quad_loop_device")
+
+    # ---- the closed loops' recorder ---------------------------------------------------------
+    def set_loop_record(self, rec):
+        """Attach a LoopRecording (or a raw abi.LoopRecord) to the plan's closed loops, or detach
+        with None (bmpc_set_loop_record).  While attached, every step of loop_device /
+        merge_loop_device / quad_loop_device writes its row; the single-step entry points do not
+        record.  The plan keeps a reference to the attached object, so its tensors stay alive."""
+        struct = getattr(rec, "struct", rec)
+        if rec is not None and struct is None:
+            raise ValueError("the recording's columns are not on a device (a host snapshot?)")
+        check(lib().bmpc_set_loop_record(self._h, None if struct is None else C.byref(struct)), "bmpc_set_loop_record")
+        self._loop_record = rec
+
+    def new_loop_record(self, capacity, t_base=0, predictions=False, device=None):
+        """A LoopRecording of `capacity` rows per ego from closed-loop step `t_base` on, in fresh
+        zeroed torch tensors on `device` (default: the plan's); predictions adds the optional
+        upred / xpred / zpred / branch_w columns (no zpred on robust plans, whose tree keeps no
+        obstacle predictions per node).  Not attached yet: pass it to set_loop_record."""
+        import torch
+        dev = torch.device("cuda", self.device) if device is None else torch.device(device)
+        B, c, n, d = self.batch, int(capacity), self.desc.n, self.desc.d
+        if c < 1:
+            raise ValueError("capacity must be at least 1")
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        cols = dict(scene=torch.zeros((B, c, abi.ENV_STRIDE), **f64), xref=torch.zeros((B, c, n), **f64),
+                    u=torch.zeros((B, c, d), **f64), J=torch.zeros((B, c), **f64),
+                    status=torch.zeros((B, c), **i32), iters=torch.zeros((B, c), **i32))
+        if predictions:
+            cols.update(upred=torch.zeros((B, c, self.U, d), **f64), xpred=torch.zeros((B, c, self.T, n), **f64),
+                        branch_w=torch.zeros((B, c, self.nbranch - 1), **f64))
+            if self.desc.controller != abi.CTRL_ROBUST:
+                cols["zpred"] = torch.zeros((B, c, self.T, n), **f64)
+        torch.cuda.synchronize(dev)   # the zero fills are done before a loop's own stream writes rows
+        return LoopRecording(SCENE_KINDS[self.desc.model], c, t_base, cols)
 
     def get_transform(self):
         """The S [B,n,n], bx [B,nFx] and (S on, bx set) flags [B,2] in the egos' transform slots."""

@@ -75,6 +75,52 @@ def xref_rule(x, z, v0=20.0):
     return xref, tgt
 
 
+def _attach_record(pl, steps, record):
+    """The recorder of a *_population call: None, or a LoopRecording of `steps` rows per ego attached
+    to the plan -- record=True the core columns, record="predictions" also uPred / xPred / zPred /
+    branch_w (BatchPlan.new_loop_record)."""
+    if not record:
+        return None
+    rec = pl.new_loop_record(steps, 0, predictions=(record == "predictions"))
+    pl.set_loop_record(rec)
+    return rec
+
+
+def overtake_population(B, steps, seed=0, device=0, record=False):
+    """`steps` closed-loop overtake steps of B seeded episodes (seeded_batch: row 0 is
+    sim_overtake's initial state), resident on the GPU (BatchPlan.loop_device).  Returns the per-ego
+    statistics rows [B, ENV_NSTAT] (the form distributed.episode_stats takes; a step's solve is
+    booked by the next step, so they cover steps - 1 solves) and the final scene [B, ENV_STRIDE];
+    with `record` also the per-step record on the host (plan.LoopRecording: row t holds step t,
+    the last row's scene is the returned one)."""
+    import torch
+    from . import plan
+    x, z, _, tgt = seeded_batch(B, seed)
+    pl = plan.BatchPlan(highway_desc(), B, device)
+    pl.set_policies(highway_policy_rows(tgt))
+    dev = torch.device("cuda", device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
+    scene[:, abi.ENV_X:abi.ENV_X + 4] = torch.tensor(x, **f64)
+    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = torch.tensor(z, **f64)
+    up = torch.zeros((B, pl.U, 2), **f64)
+    J = torch.zeros(B, **f64)
+    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
+    tx, tz, tr = (torch.zeros((B, 4), **f64) for _ in range(3))
+    rec = _attach_record(pl, steps, record)
+    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
+    stream = torch.cuda.Stream(dev)
+    pl.loop_device(abi.make_env(), 0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(),
+                   tr.data_ptr(), J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+    stream.synchronize()
+    out = stats.cpu().numpy(), scene.cpu().numpy()
+    if rec is not None:
+        out += (rec.host(),)
+    pl.close()
+    return out
+
+
 def merge_desc(N=40, NB=1, N_lane=2, am=7.0, rm=0.3, L=4.0, W=2.5, s1=2.0, ralpha=0.1):
     """main_branch.sim_merge (:53-88): initBranchMPC(4, 2, 40, 1, ..., N_lane=2) driving
     BranchMPC_CVaR(ralpha=0.1) over PredictiveModel_merge's main-road model (pred_model[0])."""
@@ -116,11 +162,12 @@ def seeded_merge_batch(B, seed=0):
     return x, z
 
 
-def merge_population(B, steps, seed=0, device=0):
+def merge_population(B, steps, seed=0, device=0, record=False):
     """`steps` closed-loop merge steps of B seeded episodes, resident on the GPU
     (BatchPlan.merge_loop_device).  Returns the per-ego statistics rows [B, ENV_NSTAT] (the form
     distributed.episode_stats takes; a step's solve is booked by the next step, so they cover
-    steps - 1 solves) and the final scene [B, ENV_STRIDE]."""
+    steps - 1 solves) and the final scene [B, ENV_STRIDE]; with `record` (overtake_population's)
+    also the per-step record on the host."""
     import torch
     from . import plan
     x, z = seeded_merge_batch(B, seed)
@@ -137,12 +184,15 @@ def merge_population(B, steps, seed=0, device=0):
     st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
     tx, tz, tr = (torch.zeros((B, 4), **f64) for _ in range(3))
+    rec = _attach_record(pl, steps, record)
     torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
     stream = torch.cuda.Stream(dev)
     pl.merge_loop_device(0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(), tr.data_ptr(),
                          J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
     stream.synchronize()
     out = stats.cpu().numpy(), scene.cpu().numpy()
+    if rec is not None:
+        out += (rec.host(),)
     pl.close()
     return out
 
@@ -197,12 +247,12 @@ def quad_scene(x, z, x_des):
     return scene
 
 
-def quadruped_population(B, steps, seed=0, device=0):
+def quadruped_population(B, steps, seed=0, device=0, record=False):
     """`steps` closed-loop main_quadruped steps of B seeded episodes (seeded_quadruped_batch, each
     ego walking to a goal of its own), resident on the GPU (BatchPlan.quad_loop_device).  Returns
     the per-ego statistics rows [B, ENV_NSTAT] (the form distributed.episode_stats takes; a step's
     solve is booked by the next step, so they cover steps - 1 solves) and the final scene
-    [B, ENV_STRIDE]."""
+    [B, ENV_STRIDE]; with `record` (overtake_population's) also the per-step record on the host."""
     import torch
     from . import plan
     x, z, _ = seeded_quadruped_batch(B, seed)
@@ -216,12 +266,15 @@ def quadruped_population(B, steps, seed=0, device=0):
     st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
     tx, tz, tr = (torch.zeros((B, 3), **f64) for _ in range(3))
+    rec = _attach_record(pl, steps, record)
     torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
     stream = torch.cuda.Stream(dev)
     pl.quad_loop_device(abi.make_quad_env(), 0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(),
                         tr.data_ptr(), J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
     stream.synchronize()
     out = stats.cpu().numpy(), scene.cpu().numpy()
+    if rec is not None:
+        out += (rec.host(),)
     pl.close()
     return out
 

@@ -18,6 +18,7 @@
 #include "bmpc_plan.h"
 #include "bmpc_qp.h"
 #include "bmpc_qpplan.h"
+#include "bmpc_record.h"
 #include "bmpc_solve.h"
 
 namespace bmpc {
@@ -445,6 +446,39 @@ __device__ __attribute__((noinline)) void loop_quad_env_step(const bmpc_quad_env
   quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr);
 }
 
+// Ego e's row r of the closed loops' recorder (bmpc_record.h), by the 64 lanes of one wave: the
+// scene row st, the solve's x_ref xr, its uPred up, cost and exit code from the loop's own buffers,
+// the predictions, the tree's obstacle predictions and the branch weights out of the ego's slab w
+// through the plan's base layout -- the offsets bmpc_get_tree and write_outputs read (none of them
+// lies in a span the small-batch kernel relocates to LDS, bmpc_hip.hip blk_layouts).
+__device__ __forceinline__ void record_ego_row(const bmpc_loop_record& R, const Plan& P, const Layout& L, int e,
+                                               size_t r, const double* w, const double* st, const double* xr,
+                                               const double* up, const double* J, const int32_t* status,
+                                               const int32_t* iters) {
+  const RecordDims D{P.n, P.d, P.T, P.U, P.nbranch - 1};
+  const RecordSrc S{st, xr, up, J, status, iters, w + L.xpred, w + L.zbar, w + L.w + 1};
+  record_write_row(R, D, (size_t)e, r, (int)threadIdx.x, 64, S);
+}
+// ... as calls of their own at the end of a k_loop step: their registers are allocated apart from
+// the solve's (the IPM / QP loop's 128-VGPR budget never sees the copy loops; DESIGN §5b on what
+// inlining into that budget costs), and a loop without a recorder branches around them.  Two calls
+// of scalar arguments, not one taking the struct: an 88-byte struct goes to a callee through the
+// caller's stack frame, which every k_loop launch would pay as scratch, recorder or not (§5e);
+// each of these fits the 32 argument registers.  `row` = e * capacity + r.
+__device__ __attribute__((noinline)) void loop_record_core(double* scene, double* xref, double* u, double* J,
+                                                           int32_t* status, int32_t* iters, size_t row,
+                                                           const Plan& P, const double* st, const double* xr,
+                                                           const double* up, const double* Je, const int32_t* ste,
+                                                           const int32_t* ite) {
+  record_write_core(scene, xref, u, J, status, iters, row, P.n, P.d, (int)threadIdx.x, 64, st, xr, up, Je, ste, ite);
+}
+__device__ __attribute__((noinline)) void loop_record_wide(double* upred, double* xpred, double* zpred, double* bw,
+                                                           size_t row, const Plan& P, const Layout& L,
+                                                           const double* w, const double* up) {
+  const RecordDims D{P.n, P.d, P.T, P.U, P.nbranch - 1};
+  record_write_wide(upred, xpred, zpred, bw, row, D, (int)threadIdx.x, 64, up, w + L.xpred, w + L.zbar, w + L.w + 1);
+}
+
 #ifndef BMPC_MERGE_LOOP_INLINE_IPM
 #define BMPC_MERGE_LOOP_INLINE_IPM 1
 #endif
@@ -494,12 +528,18 @@ struct QuadScene {
 // that order, per step -- the same per-ego functions the three launches run, so the same bits --
 // with no device-wide boundary between the steps: the egos' loops are independent, and a wave
 // whose ego needs few IPM iterations in one step starts its next step instead of idling until the
-// slowest ego of the batch finishes.
-template <class M, bool TL, class SC>
+// slowest ego of the batch finishes.  REC: the kernel can record (bmpc_set_loop_record) -- the one
+// instantiation the product launches, with or without a recorder; a build with
+// -DBMPC_LOOP_RECORD_TEMPLATE=1 launches the REC = false instantiation, which compiles as the kernel
+// did before the recorder, whenever none is attached (the A/B of DESIGN §5e).
+#ifndef BMPC_LOOP_RECORD_TEMPLATE
+#define BMPC_LOOP_RECORD_TEMPLATE 0
+#endif
+template <class M, bool TL, class SC, bool REC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) void k_loop(
     const Bundle* __restrict__ B, double* __restrict__ ws, bmpc_policy* __restrict__ pol, SC sc, int t0,
     int nsteps, double* scene, double* upred, double* xs, double* zs, double* xrefs, double* J, int32_t* status,
-    int32_t* iters, double* stats, int batch) {
+    int32_t* iters, double* stats, int batch, bmpc_loop_record rec) {
   const int e = blockIdx.x;
   if (e >= batch) return;
   const Plan& P = B->P;
@@ -539,6 +579,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
       status[e] = r.exit_flag;
       iters[e] = r.iters;
     }
+    // the step's row of the recorder (a kernel argument: a wave-uniform scalar branch); each lane
+    // reads back what it stored above itself, the rest was written before the solve's last barrier
+    if constexpr (REC) {
+      if (rec.capacity > 0) {
+        size_t r;
+        if (record_row_of(rec, t, &r)) {
+          const size_t row = record_offset((size_t)e, (size_t)rec.capacity, r, 1);
+          loop_record_core(rec.scene, rec.xref, rec.u, rec.J, rec.status, rec.iters, row, P, st, xr, up, J + e,
+                           status + e, iters + e);
+          if (rec.upred || rec.xpred || rec.zpred || rec.branch_w)
+            loop_record_wide(rec.upred, rec.xpred, rec.zpred, rec.branch_w, row, P, L, w, up);
+        }
+      }
+    }
     __syncthreads();
   }
 }
@@ -563,6 +617,7 @@ struct SolveLaunch {
   const Plan* hplan = nullptr;       // the plan on the host (launch sizes)
   size_t blk_hot_off = 0;            // ... their LDS offset (doubles)
   const struct PhasedLaunch* ph = nullptr;   // tools-only builds (BMPC_WITH_PHASED, below)
+  bmpc_loop_record rec = {};         // the fused closed loop's recorder (capacity 0: none)
 };
 using LaunchFn = hipError_t(const SolveLaunch&);
 
@@ -614,12 +669,16 @@ hipError_t launch_solver(const SolveLaunch& a) {
 template <class M, class SC>
 hipError_t launch_loop(const SolveLaunch& a, const SC& sc, int t0, int nsteps, double* scene, double* stats) {
   void (*k)(const Bundle*, double*, bmpc_policy*, SC, int, int, double*, double*, double*, double*, double*, double*,
-            int32_t*, int32_t*, double*, int) = a.rich ? k_loop<M, true, SC> : k_loop<M, false, SC>;
+            int32_t*, int32_t*, double*, int, bmpc_loop_record) =
+      a.rich ? k_loop<M, true, SC, true> : k_loop<M, false, SC, true>;
+  if constexpr (BMPC_LOOP_RECORD_TEMPLATE != 0) {
+    if (a.rec.capacity < 1) k = a.rich ? k_loop<M, true, SC, false> : k_loop<M, false, SC, false>;
+  }
   const hipError_t e = optin_lds((const void*)k, a.lds_bytes);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(a.batch), dim3(64), a.lds_bytes, a.stream, a.bundle, a.ws, const_cast<bmpc_policy*>(a.pol),
                      sc, t0, nsteps, scene, a.upred, const_cast<double*>(a.x), const_cast<double*>(a.z),
-                     const_cast<double*>(a.xref), a.J, a.status, a.iters, stats, a.batch);
+                     const_cast<double*>(a.xref), a.J, a.status, a.iters, stats, a.batch, a.rec);
   return hipGetLastError();
 }
 

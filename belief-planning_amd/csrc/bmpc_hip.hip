@@ -80,6 +80,24 @@ __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, i
                     xref + (size_t)e * 3);
 }
 
+// One wave per ego: step t's row of the closed loops' recorder after the per-step launches (run_loop)
+// -- the fused k_loop's writer (record_ego_row) on the loop's buffers and the slab, so the same
+// bits.  A wave per ego, not a flat grid over elements: the grid and the lane striding are the
+// solver kernels' own, each row goes out in contiguous 512-byte segments, and the offsets are
+// computed once per ego, not per element.  The host launches it only for a step inside the window.
+__global__ __launch_bounds__(64) void k_loop_record(const Bundle* __restrict__ B, const double* __restrict__ ws,
+                                                    bmpc_loop_record R, int t, int batch, const double* scene,
+                                                    const double* xref, const double* upred, const double* J,
+                                                    const int32_t* status, const int32_t* iters) {
+  const int e = blockIdx.x;
+  size_t r;
+  if (e >= batch || !record_row_of(R, t, &r)) return;
+  const Plan& P = B->P;
+  const Layout& L = B->L;
+  record_ego_row(R, P, L, e, r, ws + L.stride * (size_t)e, scene + (size_t)e * ENV_STRIDE, xref + (size_t)e * P.n,
+                 upred + (size_t)e * P.U * P.d, J + e, status + e, iters + e);
+}
+
 __global__ void k_gather(const double* __restrict__ ws, size_t stride, size_t off, int count,
                          double* __restrict__ out, int batch) {
   const size_t tot = (size_t)batch * count;
@@ -356,6 +374,7 @@ struct bmpc_plan {
   bmpc_merge_env_desc menv = {};
   double* d_mref = nullptr;
   int n_mref = 0;   // 0: no merge scene set
+  bmpc_loop_record rec = {};   // the closed loops' recorder (bmpc_set_loop_record; capacity 0: none)
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
 
@@ -787,11 +806,13 @@ extern "C++" {
 // nsteps closed-loop steps of a scene (bmpc_loop_device, bmpc_merge_loop_device): one k_loop launch
 // (`fused`) for batches that choose_launch lets fuse, otherwise the scene's step (`step`) + the
 // solve launches per step -- same results either way.  retargets: the scene's step rewrites d_pol;
-// qp_loop: the scene's k_loop runs the QP solver (choose_launch).
+// qp_loop: the scene's k_loop runs the QP solver (choose_launch).  The plan's recorder
+// (bmpc_set_loop_record) rides along either way: k_loop takes it as an argument; the per-step path
+// launches k_loop_record after each solve whose step lies in the window.
 template <class Step, class Fused>
-static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_upred, double* d_x, double* d_z,
-                    double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters, void* stream, Step step,
-                    Fused fused) {
+static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_scene, double* d_upred,
+                    double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
+                    void* stream, Step step, Fused fused) {
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
   const LaunchChoice ch = choose_launch(pl, plan_takes_transform(pl->hp.plan), qp_loop);
@@ -799,10 +820,17 @@ static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nst
     for (int k = 0; k < nsteps; ++k) {
       if (int rc = step(t0 + k)) return rc;
       if (int rc = launch_solve(pl, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters, s)) return rc;
+      size_t row;
+      if (record_row_of(pl->rec, t0 + k, &row)) {
+        hipLaunchKernelGGL(k_loop_record, dim3(pl->batch), dim3(64), 0, s, pl->d_bundle, pl->d_ws, pl->rec, t0 + k,
+                           pl->batch, d_scene, d_xref, d_upred, d_J, d_status, d_iters);
+        HIPCHECK(hipGetLastError());
+      }
     }
     return 0;
   }
-  const SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
+  SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
+  a.rec = pl->rec;
   pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
   // (the whole fused launch is booked as the solver's time, none as the tree's)
   if (const int rc = timing_mark(pl, s, 0)) return rc;
@@ -885,7 +913,7 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_loop_device: nsteps >= 1 and t0 >= 0");
   if (env->n_lane < 1) return fail(-22, "bmpc_loop_device: n_lane < 1");
   return run_loop(
-      pl, true, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, true, false, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
       },
@@ -943,7 +971,7 @@ int bmpc_merge_loop_device(bmpc_plan* pl, int t0, int nsteps, double* d_scene, d
   if (!pl->n_mref) return fail(-22, "bmpc_merge_loop_device: no merge scene (bmpc_set_merge_scene)");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_merge_loop_device: nsteps >= 1 and t0 >= 0");
   return run_loop(
-      pl, false, false, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, false, false, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_merge_env_step(pl, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
       },
@@ -983,12 +1011,27 @@ int bmpc_quad_loop_device(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t0, 
     return fail(-22, "bmpc_quad_loop_device: " + e);
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_quad_loop_device: nsteps >= 1 and t0 >= 0");
   return run_loop(
-      pl, false, true, t0, nsteps, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, false, true, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_quad_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats,
                                   stream);
       },
       [&](const SolveLaunch& a) { return launch_loop_quad(a, *env, t0, nsteps, d_scene, d_stats); });
+}
+
+int bmpc_set_loop_record(bmpc_plan* pl, const bmpc_loop_record* rec) {
+  if (!pl) return fail(-22, "null argument");
+  if (!rec) {
+    pl->rec = bmpc_loop_record{};
+    return 0;
+  }
+  if (rec->capacity < 1) return fail(-22, "bmpc_set_loop_record: capacity must be at least 1");
+  if (!rec->scene || !rec->xref || !rec->u || !rec->J || !rec->status || !rec->iters)
+    return fail(-22, "bmpc_set_loop_record: null core column (scene, xref, u, J, status and iters are required)");
+  if (rec->zpred && pl->hp.plan.desc.controller == BMPC_CTRL_ROBUST)
+    return fail(-22, "bmpc_set_loop_record: a robustMPC plan's tree keeps no zbar: zpred must be NULL");
+  pl->rec = *rec;
+  return 0;
 }
 
 static int gather(bmpc_plan* pl, size_t off, int count, double* host) {

@@ -417,6 +417,50 @@ int bmpc_quad_loop_device(bmpc_plan* plan, const bmpc_quad_env_desc* env, int t0
                           double* d_scene, double* d_upred, double* d_x, double* d_z, double* d_xref,
                           double* d_J, int32_t* d_status, int32_t* d_iters, double* d_stats, void* stream);
 
+/* The closed loops' per-step recorder: what the reference's own loops keep of an episode --
+ * Highway_sim's state_rec / input_rec / backup_choice_rec / xPred_rec / zPred_rec / branch_w_rec
+ * (Highway_env_branch.py:393-444) and quadruped_env.sim's -- written on the device by every step of
+ * bmpc_loop_device, bmpc_merge_loop_device and bmpc_quad_loop_device, on whichever launch path the
+ * plan takes (one fused k_loop launch or the launches per step).
+ *
+ * A row is in the device scene's own convention, state and inputs OF step t: the scene row holds
+ * the ego x and obstacle z that step t's solve was given, the obstacle's backup choice and input of
+ * step t, the collision flag and the step count t + 1; u is the input that solve returned, which
+ * the Euler step of t + 1 applies.  Highway_sim records after the step: its state_rec[t] is row
+ * t + 1's x (and z), its input_rec[t] is row t's u, its backup_choice_rec[t], xPred_rec[t],
+ * zPred_rec[t] and branch_w_rec[t] are row t's.  The state after the last recorded input is not in
+ * the record (no step computed it); it is the first row of the loop's continuation. */
+typedef struct {
+  int32_t capacity;   /* rows per ego, >= 1 */
+  int32_t t_base;     /* row r of an ego holds closed-loop step t_base + r; a step outside
+                         [t_base, t_base + capacity) is not recorded and touches nothing */
+  /* core columns, all required (device pointers, caller-owned, ego-major) */
+  double*  scene;     /* [batch][capacity][BMPC_ENV_STRIDE]  the ego's scene row as step t's solve saw it
+                         (after the scene step of t, before the Euler step of t+1) */
+  double*  xref;      /* [batch][capacity][n]   the solve's x_ref (x and z are in the scene row) */
+  double*  u;         /* [batch][capacity][d]   uPred[0] of step t's solve: the input applied next */
+  double*  J;         /* [batch][capacity] */
+  int32_t* status;    /* [batch][capacity] */
+  int32_t* iters;     /* [batch][capacity] */
+  /* optional columns, NULL skips */
+  double*  upred;     /* [batch][capacity][U][d] */
+  double*  xpred;     /* [batch][capacity][T][n] */
+  double*  zpred;     /* [batch][capacity][T][n]  the tree's obstacle predictions (zbar of bmpc_get_tree) */
+  double*  branch_w;  /* [batch][capacity][nbranch-1] */
+} bmpc_loop_record;
+
+/* Attach (copy of *rec kept with the plan) or detach (rec == NULL) the recorder of the plan's
+ * closed loops.  Host state only: nothing is enqueued or waited for, and the struct travels to the
+ * kernels by value, so a loop already enqueued keeps the recorder it was launched with.  While
+ * attached, every step run by the three loop entry points writes its row; a loop continued over
+ * several calls fills consecutive rows (rows are addressed by t, not by call).  The single-step
+ * entry points (bmpc_env_step, bmpc_solve_device, ...) do not record.  The loops' other results --
+ * scene, outputs, statistics, warm start -- are the same bits with and without a recorder.  The
+ * columns must stay allocated until the last loop launched with them has finished.  -22 with a
+ * message for capacity < 1, a NULL core column, or zpred on a BMPC_CTRL_ROBUST plan (its tree
+ * keeps no obstacle prediction per state node). */
+int bmpc_set_loop_record(bmpc_plan* plan, const bmpc_loop_record* rec);
+
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of
  * the graph of calc_xp_expr (:238-276).  M agents (1..4), m backups (1..4), nb = 4 + M*m.
