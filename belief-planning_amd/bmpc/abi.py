@@ -116,6 +116,37 @@ class LoopRecord(C.Structure):
                 ("upred", C.c_void_p), ("xpred", C.c_void_p), ("zpred", C.c_void_p), ("branch_w", C.c_void_p)]
 
 
+OBS_ARGMAX, OBS_SAMPLE_MODEL = 0, 1   # bmpc_obstacle_sampling.mode (include/bmpc.h BMPC_OBS_*)
+OBS_MODES = {"argmax": OBS_ARGMAX, "model": OBS_SAMPLE_MODEL}
+
+
+class ObstacleSampling(C.Structure):
+    """bmpc_obstacle_sampling: how the overtake / quadruped scene's obstacle chooses its backup
+    policy (bmpc_set_obstacle_sampling; the draws are bmpc.rng's)."""
+    _fields_ = [("mode", C.c_int32), ("hold", C.c_int32), ("seed", C.c_uint64), ("ego_base", C.c_int64)]
+
+
+def make_obstacle_sampling(mode="model", seed=0, hold=1, ego_base=0):
+    """Validated bmpc_obstacle_sampling: mode "argmax" / "model" (or abi.OBS_*), a seed of 64 bits,
+    hold >= 1 closed-loop steps per sampled choice, ego_base >= 0 the global index of the plan's
+    ego 0 (a shard's first ego)."""
+    if isinstance(mode, str):
+        if mode not in OBS_MODES:
+            raise ValueError(f"obstacle sampling mode {mode!r}: one of {sorted(OBS_MODES)}")
+        mode = OBS_MODES[mode]
+    if int(mode) not in (OBS_ARGMAX, OBS_SAMPLE_MODEL):
+        raise ValueError(f"obstacle sampling mode {mode!r}: abi.OBS_ARGMAX or abi.OBS_SAMPLE_MODEL")
+    if int(hold) != hold or not 1 <= int(hold) < 2 ** 31:
+        raise ValueError("hold must be an integer of at least 1")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if int(ego_base) != ego_base or not 0 <= int(ego_base) < 2 ** 63:
+        raise ValueError("ego_base must be an integer of at least 0")
+    S = ObstacleSampling()
+    S.mode, S.hold, S.seed, S.ego_base = int(mode), int(hold), int(seed), int(ego_base)
+    return S
+
+
 def _fill(arr, values):
     v = np.asarray(values, dtype=np.float64).ravel()
     for i, x in enumerate(v):

@@ -272,6 +272,29 @@ class BatchPlan:
         check(lib().bmpc_set_loop_record(self._h, None if struct is None else C.byref(struct)), "bmpc_set_loop_record")
         self._loop_record = rec
 
+    # ---- the scenes' obstacle sampler --------------------------------------------------------
+    def set_obstacle_sampling(self, mode="model", seed=0, hold=1, ego_base=0):
+        """How the obstacle of the plan's overtake or quadruped scene chooses its backup policy
+        (bmpc_set_obstacle_sampling).  mode "model": at every closed-loop step t with t % hold == 0
+        the obstacle draws its policy from the model's own branch distribution p_j(x, z) at the
+        step's state -- the smallest j with u < p_0 + ... + p_j for
+        u = bmpc.rng.obstacle_uniform(seed, ego_base + e, t // hold) -- and keeps it for `hold`
+        steps; a sampler attached mid-episode keeps the scene row's last choice until the next
+        such step.  mode None or "argmax" detaches: the reference's deterministic rule.  A plan
+        holding egos lo..hi-1 of a sharded population passes ego_base=lo (distributed.shard): every
+        ego then gets the trajectory it has in the unsharded run.  Host state only; loop_device /
+        quad_loop_device on either launch path and the single-step env_step_device /
+        quad_env_step_device obey it.  Also takes an abi.ObstacleSampling."""
+        if mode is None:
+            struct = None
+        elif isinstance(mode, abi.ObstacleSampling):
+            struct = mode
+        else:
+            struct = abi.make_obstacle_sampling(mode, seed, hold, ego_base)
+        check(lib().bmpc_set_obstacle_sampling(self._h, None if struct is None else C.byref(struct)),
+              "bmpc_set_obstacle_sampling")
+        self.obstacle_sampling = struct
+
     def new_loop_record(self, capacity, t_base=0, predictions=False, device=None):
         """A LoopRecording of `capacity` rows per ego from closed-loop step `t_base` on, in fresh
         zeroed torch tensors on `device` (default: the plan's); predictions adds the optional

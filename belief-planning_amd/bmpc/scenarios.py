@@ -86,18 +86,55 @@ def _attach_record(pl, steps, record):
     return rec
 
 
+def _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base):
+    """The obstacle sampler of a sampled_*_population call: obstacle=None leaves the plan on the
+    reference's deterministic rule, "model" attaches BatchPlan.set_obstacle_sampling("model", ...)."""
+    if obstacle is None:
+        return None
+    if obstacle != "model":
+        raise ValueError(f"obstacle={obstacle!r}: None (the reference's rule) or 'model'")
+    pl.set_obstacle_sampling("model", seed=obstacle_seed, hold=hold, ego_base=ego_base)
+    return pl.obstacle_sampling
+
+
+def _shard_rows(B, ego_base, population):
+    """Rows [ego_base, ego_base + B) of a population of `population` egos (default: ends with them)."""
+    lo = int(ego_base)
+    total = lo + B if population is None else int(population)
+    if lo < 0 or B < 1 or lo + B > total:
+        raise ValueError(f"egos {lo}..{lo + B - 1} do not lie in a population of {total}")
+    return total, slice(lo, lo + B)
+
+
 def overtake_population(B, steps, seed=0, device=0, record=False):
     """`steps` closed-loop overtake steps of B seeded episodes (seeded_batch: row 0 is
     sim_overtake's initial state), resident on the GPU (BatchPlan.loop_device).  Returns the per-ego
     statistics rows [B, ENV_NSTAT] (the form distributed.episode_stats takes; a step's solve is
     booked by the next step, so they cover steps - 1 solves) and the final scene [B, ENV_STRIDE];
     with `record` also the per-step record on the host (plan.LoopRecording: row t holds step t,
-    the last row's scene is the returned one)."""
+    the last row's scene is the returned one).  The obstacle follows the reference's deterministic
+    rule; sampled_overtake_population draws its policy from the model's branch distribution."""
+    return sampled_overtake_population(B, steps, seed, device, record, obstacle=None)
+
+
+def sampled_overtake_population(B, steps, seed=0, device=0, record=False, obstacle="model", obstacle_seed=0, hold=1,
+                                ego_base=0, population=None, desc=None):
+    """overtake_population with an obstacle that draws its backup policy from the model's own branch
+    distribution (obstacle="model": BatchPlan.set_obstacle_sampling with seed `obstacle_seed`, a
+    choice kept for `hold` steps; obstacle=None is overtake_population itself).  The B egos are rows
+    ego_base .. ego_base + B - 1 of seeded_batch(population, seed) (population defaults to
+    ego_base + B) and draw as those global egos: a sharded run passes
+    ego_base = distributed.shard(population, rank, world)[0] and B = hi - lo on every rank, and each
+    ego then has the trajectory it has in the unsharded run.  desc: another highway plan description
+    than highway_desc().  Any draw can be audited on the host with bmpc.rng.obstacle_uniform(
+    obstacle_seed, global ego, t // hold)."""
     import torch
     from . import plan
-    x, z, _, tgt = seeded_batch(B, seed)
-    pl = plan.BatchPlan(highway_desc(), B, device)
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
+    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
     pl.set_policies(highway_policy_rows(tgt))
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
     scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
@@ -252,15 +289,27 @@ def quadruped_population(B, steps, seed=0, device=0, record=False):
     ego walking to a goal of its own), resident on the GPU (BatchPlan.quad_loop_device).  Returns
     the per-ego statistics rows [B, ENV_NSTAT] (the form distributed.episode_stats takes; a step's
     solve is booked by the next step, so they cover steps - 1 solves) and the final scene
-    [B, ENV_STRIDE]; with `record` (overtake_population's) also the per-step record on the host."""
+    [B, ENV_STRIDE]; with `record` (overtake_population's) also the per-step record on the host.
+    The obstacle follows the reference's deterministic rule; sampled_quadruped_population draws its
+    policy from the model's branch distribution."""
+    return sampled_quadruped_population(B, steps, seed, device, record, obstacle=None)
+
+
+def sampled_quadruped_population(B, steps, seed=0, device=0, record=False, obstacle="model", obstacle_seed=0, hold=1,
+                                 ego_base=0, population=None, desc=None):
+    """quadruped_population with the sampled obstacle: sampled_overtake_population's arguments and
+    sharding rule (rows ego_base .. ego_base + B - 1 of seeded_quadruped_batch(population, seed) and
+    of seeded_quadruped_goals; a sharded run passes ego_base = distributed.shard(...)[0])."""
     import torch
     from . import plan
-    x, z, _ = seeded_quadruped_batch(B, seed)
-    pl = plan.BatchPlan(quadruped_desc(), B, device)
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
+    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
     pl.set_policies(quadruped_policy_rows(B))
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
-    scene = torch.tensor(quad_scene(x, z, seeded_quadruped_goals(B, seed)), **f64)
+    scene = torch.tensor(quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), **f64)
     up = torch.zeros((B, pl.U, 3), **f64)
     J = torch.zeros(B, **f64)
     st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))

@@ -17,6 +17,7 @@
 #pragma once
 
 #include "bmpc_model.h"
+#include "bmpc_rng.h"
 
 namespace bmpc {
 
@@ -70,13 +71,31 @@ BMPC_HD void env_policy_u(int kind, const double* x, double Kpsi, const double* 
   }
 }
 
+// The sampled backup choice of step t (bmpc_set_obstacle_sampling, BMPC_OBS_SAMPLE_MODEL) of the
+// plan's ego e at the pre-step state (x, z): at an epoch start, t % hold == 0, the inverse CDF of
+// the model's own branch distribution -- branch_eval's p_j = prob_weight(bf_traj_j) / sum, in plain
+// doubles, no Jacobian -- at the draw of (seed, ego_base + e, t / hold); otherwise `prev`, the scene
+// row's choice of the step before (clamped to a policy: a sampler attached mid-episode, or a row
+// the caller wrote, keeps it until the next epoch boundary).  mc: the plan's model constants.
+template <class M>
+BMPC_HD int env_sampled_choice(const bmpc_obstacle_sampling& S, long long e, const double* mc, double dt, int N,
+                               int m, int t, const bmpc_policy* pol, const double* x, const double* z, double prev) {
+  if (t % S.hold != 0) return prev >= (double)(m - 1) ? m - 1 : prev > 0.0 ? (int)prev : 0;
+  double w[BMPC_MAX_M];
+  for (int j = 0; j < m; ++j) w[j] = M::prob_weight(mc, M::bf_traj(mc, dt, N, pol[0], pol[j], x, z));
+  return rng_inverse_cdf(w, m, obstacle_uniform(S.seed, (uint64_t)(S.ego_base + e), (uint32_t)(t / S.hold)));
+}
+BMPC_HD bool env_samples(const bmpc_obstacle_sampling* smp) { return smp && smp->mode == BMPC_OBS_SAMPLE_MODEL; }
+
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; pol: the
 // ego's m model policies (the lane-change target is re-targeted in place, update_backup);
 // u0: uPred[0] of the last solve (unused at t == 0); x_out, z_out, xref_out: the next
-// solve's inputs.
+// solve's inputs.  smp: the plan's obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the
+// reference's argmax rule), with mc, the plan's model constants, and e, the ego's index in the plan.
 BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t, double* st,
                           bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
-                          double* xref_out) {
+                          double* xref_out, const bmpc_obstacle_sampling* smp = nullptr,
+                          const double* mc = nullptr, long long e = 0) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
@@ -90,39 +109,43 @@ BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t
     const double dis = fmax(fabs(x[0] - z[0]) - E.vlen, fabs(x[1] - z[1]) - E.vwid);
     if (dis < 0.0) st[ENV_COLL] = 1.0;
   }
-  // safety value of every obstacle backup against the ego's backup-0 rollout (the ego's
-  // backupidx is never changed): min over the rows of veh_col and lane_bdry_h of the ego
-  const double s0 = E.L + 1.0, s1 = E.W + 0.2;
-  const double lb = E.W / 2.0, ub = E.n_lane * 3.6 - E.W / 2.0;
-  double hi[BMPC_MAX_M], zo[BMPC_MAX_M][4], xe[4];
-  double lane_min = 1e300;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) xe[i] = x[i];
-  for (int j = 0; j < m; ++j) {
-    hi[j] = 1e300;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) zo[j][i] = z[i];
-  }
-  for (int k = 0; k < N; ++k) {
-    double ue[2], fe[4];
-    Highway::policy(pol[0], xe, ue);
-    Highway::f(xe, ue, fe);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xe[i] = xe[i] + fe[i] * dt;
-    lane_min = fmin(lane_min, env_lane_bdry(xe[1], lb, ub));
-    for (int j = 0; j < m; ++j) {
-      double uo[2], fo[4];
-      Highway::policy(pol[j], zo[j], uo);
-      Highway::f(zo[j], uo, fo);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) zo[j][i] = zo[j][i] + fo[i] * dt;
-      hi[j] = fmin(hi[j], env_veh_col(xe[0], xe[1], zo[j][0], zo[j][1], s0, s1));
-    }
-  }
   int best = 0;
-  for (int j = 0; j < m; ++j) {
-    hi[j] = fmin(hi[j], lane_min);
-    if (hi[j] > hi[best]) best = j;   // np.argmax: the first maximum
+  if (env_samples(smp)) {   // (the policies in force before this step's re-targeting below)
+    best = env_sampled_choice<Highway>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL]);
+  } else {
+    // safety value of every obstacle backup against the ego's backup-0 rollout (the ego's
+    // backupidx is never changed): min over the rows of veh_col and lane_bdry_h of the ego
+    const double s0 = E.L + 1.0, s1 = E.W + 0.2;
+    const double lb = E.W / 2.0, ub = E.n_lane * 3.6 - E.W / 2.0;
+    double hi[BMPC_MAX_M], zo[BMPC_MAX_M][4], xe[4];
+    double lane_min = 1e300;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xe[i] = x[i];
+    for (int j = 0; j < m; ++j) {
+      hi[j] = 1e300;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) zo[j][i] = z[i];
+    }
+    for (int k = 0; k < N; ++k) {
+      double ue[2], fe[4];
+      Highway::policy(pol[0], xe, ue);
+      Highway::f(xe, ue, fe);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) xe[i] = xe[i] + fe[i] * dt;
+      lane_min = fmin(lane_min, env_lane_bdry(xe[1], lb, ub));
+      for (int j = 0; j < m; ++j) {
+        double uo[2], fo[4];
+        Highway::policy(pol[j], zo[j], uo);
+        Highway::f(zo[j], uo, fo);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zo[j][i] = zo[j][i] + fo[i] * dt;
+        hi[j] = fmin(hi[j], env_veh_col(xe[0], xe[1], zo[j][0], zo[j][1], s0, s1));
+      }
+    }
+    for (int j = 0; j < m; ++j) {
+      hi[j] = fmin(hi[j], lane_min);
+      if (hi[j] > hi[best]) best = j;   // np.argmax: the first maximum
+    }
   }
   // lane bookkeeping (Python round = half to even = rint) and update_backup re-targeting
   for (int i = 0; i < 2; ++i) {

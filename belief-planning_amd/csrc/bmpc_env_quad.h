@@ -40,10 +40,12 @@ BMPC_HD double quad_env_robot_col(const double* mc, double a0, double a1, double
 
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; mc: the plan's
 // model constants; pol: the ego's m model policies; u0: uPred[0] of the last solve (unused at
-// t == 0); x_out, z_out, xref_out: the next solve's inputs (3 doubles each).
+// t == 0); x_out, z_out, xref_out: the next solve's inputs (3 doubles each).  smp: the plan's
+// obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the reference's rule); e: the ego's
+// index in the plan.
 BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, double dt, int N, int m, int t,
                                double* st, const bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
-                               double* xref_out) {
+                               double* xref_out, const bmpc_obstacle_sampling* smp = nullptr, long long e = 0) {
   double* x = st + QENV_X;
   double* z = st + QENV_Z;
   if (t > 0) {   // post(t-1): robot.step of ego and obstacle
@@ -53,27 +55,31 @@ BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, do
 #pragma unroll
     for (int i = 0; i < 3; ++i) x[i] = xp[i], z[i] = zp[i];
   }
-  // clearance of every obstacle backup against the ego's policy-0 rollout (the ego's backupidx
-  // is never changed): the rollouts of zpred_eval, row by row (rollout<> of one step, in place)
-  double hi[BMPC_MAX_M], zo[BMPC_MAX_M][3], xe[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) xe[i] = x[i];
-  for (int j = 0; j < m; ++j) {
-    hi[j] = 1e300;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) zo[j][i] = z[i];
-  }
-  for (int k = 0; k < N; ++k) {
-    rollout<Quadruped>(dt, 1, pol[0], xe, xe, 3);
-    for (int j = 0; j < m; ++j) {
-      rollout<Quadruped>(dt, 1, pol[j], zo[j], zo[j], 3);
-      hi[j] = fmin(hi[j], quad_env_robot_col(mc, xe[0], xe[1], zo[j][0], zo[j][1]));
-    }
-  }
   int best = 0;
-  if (!(hi[0] > E.switch_clearance))
-    for (int j = 1; j < m; ++j)
-      if (hi[j] > hi[best]) best = j;   // np.argmax: the first maximum
+  if (env_samples(smp)) {
+    best = env_sampled_choice<Quadruped>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL]);
+  } else {
+    // clearance of every obstacle backup against the ego's policy-0 rollout (the ego's backupidx
+    // is never changed): the rollouts of zpred_eval, row by row (rollout<> of one step, in place)
+    double hi[BMPC_MAX_M], zo[BMPC_MAX_M][3], xe[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) xe[i] = x[i];
+    for (int j = 0; j < m; ++j) {
+      hi[j] = 1e300;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) zo[j][i] = z[i];
+    }
+    for (int k = 0; k < N; ++k) {
+      rollout<Quadruped>(dt, 1, pol[0], xe, xe, 3);
+      for (int j = 0; j < m; ++j) {
+        rollout<Quadruped>(dt, 1, pol[j], zo[j], zo[j], 3);
+        hi[j] = fmin(hi[j], quad_env_robot_col(mc, xe[0], xe[1], zo[j][0], zo[j][1]));
+      }
+    }
+    if (!(hi[0] > E.switch_clearance))
+      for (int j = 1; j < m; ++j)
+        if (hi[j] > hi[best]) best = j;   // np.argmax: the first maximum
+  }
   st[ENV_OBSPOL] = (double)best;
   Quadruped::policy(pol[best], z, st + QENV_UOBS);
   // x_ref rule (:107-118): `lookahead` metres towards x_des; the heading along the way, wrapped

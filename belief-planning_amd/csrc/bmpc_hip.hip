@@ -35,17 +35,19 @@ static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, s
   return (size_t)batch <= (size_t)cus * rich || rich >= egos(solver_lds_bytes(P, transform, false));
 }
 
-// one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve
+// one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve.  smp: the plan's
+// obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device
 __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, int t, int batch, double* scene,
                       bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
-                      const int32_t* iters, int cvar, double* x, double* z, double* xref, double* stats) {
+                      const int32_t* iters, int cvar, double* x, double* z, double* xref, double* stats,
+                      bmpc_obstacle_sampling smp, const double* mc) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   double* st = scene + (size_t)e * ENV_STRIDE;
   if (t > 0 && stats && J && status && iters)
     env_accumulate(st, J[e], status[e], iters[e], cvar != 0, stats + (size_t)e * ENVS_STRIDE);
   env_step_ego(E, dt, N, m, t, st, pol + (size_t)e * m, upred ? upred + (size_t)e * U * d : nullptr,
-               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4);
+               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e);
 }
 
 // one thread per ego: the merge scene step (bmpc_env_merge.h) around the solve; S, bx and their
@@ -68,7 +70,8 @@ __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E,
 // controller (status 1 = solved)
 __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, int t, int batch, double* scene,
                            const bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
-                           const int32_t* iters, double* x, double* z, double* xref, double* stats) {
+                           const int32_t* iters, double* x, double* z, double* xref, double* stats,
+                           bmpc_obstacle_sampling smp) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   const Plan& P = B->P;
@@ -77,7 +80,7 @@ __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, i
     env_accumulate(st, J[e], status[e], iters[e], false, stats + (size_t)e * ENVS_STRIDE);
   quad_env_step_ego(E, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol + (size_t)e * P.m,
                     upred ? upred + (size_t)e * P.U * P.d : nullptr, x + (size_t)e * 3, z + (size_t)e * 3,
-                    xref + (size_t)e * 3);
+                    xref + (size_t)e * 3, &smp, e);
 }
 
 // One wave per ego: step t's row of the closed loops' recorder after the per-step launches (run_loop)
@@ -375,6 +378,7 @@ struct bmpc_plan {
   double* d_mref = nullptr;
   int n_mref = 0;   // 0: no merge scene set
   bmpc_loop_record rec = {};   // the closed loops' recorder (bmpc_set_loop_record; capacity 0: none)
+  bmpc_obstacle_sampling smp = {};   // the scenes' obstacle sampler (bmpc_set_obstacle_sampling; mode 0: none)
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
 
@@ -808,7 +812,9 @@ extern "C++" {
 // solve launches per step -- same results either way.  retargets: the scene's step rewrites d_pol;
 // qp_loop: the scene's k_loop runs the QP solver (choose_launch).  The plan's recorder
 // (bmpc_set_loop_record) rides along either way: k_loop takes it as an argument; the per-step path
-// launches k_loop_record after each solve whose step lies in the window.
+// launches k_loop_record after each solve whose step lies in the window.  The plan's obstacle sampler
+// (bmpc_set_obstacle_sampling) reaches both paths: k_loop's scene argument carries it, and `step` is
+// the single-step entry point, which passes it to k_env / k_env_quad.
 template <class Step, class Fused>
 static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_scene, double* d_upred,
                     double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
@@ -831,6 +837,7 @@ static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nst
   }
   SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
   a.rec = pl->rec;
+  a.smp = pl->smp;
   pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
   // (the whole fused launch is booked as the solver's time, none as the tree's)
   if (const int rc = timing_mark(pl, s, 0)) return rc;
@@ -894,7 +901,8 @@ int bmpc_env_step(bmpc_plan* pl, const bmpc_env_desc* env, int t, double* d_scen
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env, dim3((pl->batch + 63) / 64), dim3(64), 0, s, *env, P.desc.dt, P.N, P.m, P.U, P.d, t,
                      pl->batch, d_scene, pl->d_pol, d_upred, d_J, d_status, d_iters,
-                     P.desc.controller == BMPC_CTRL_CVAR ? 1 : 0, d_x, d_z, d_xref, d_stats);
+                     P.desc.controller == BMPC_CTRL_CVAR ? 1 : 0, d_x, d_z, d_xref, d_stats, pl->smp,
+                     pl->d_bundle->P.desc.mc);
   HIPCHECK(hipGetLastError());
   pl->pol_on_device = true;
   return 0;
@@ -997,7 +1005,7 @@ int bmpc_quad_env_step(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t, doub
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env_quad, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, *env, t, pl->batch, d_scene,
-                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats);
+                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, pl->smp);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1031,6 +1039,31 @@ int bmpc_set_loop_record(bmpc_plan* pl, const bmpc_loop_record* rec) {
   if (rec->zpred && pl->hp.plan.desc.controller == BMPC_CTRL_ROBUST)
     return fail(-22, "bmpc_set_loop_record: a robustMPC plan's tree keeps no zbar: zpred must be NULL");
   pl->rec = *rec;
+  return 0;
+}
+
+int bmpc_set_obstacle_sampling(bmpc_plan* pl, const bmpc_obstacle_sampling* smp) {
+  if (!pl) return fail(-22, "null argument");
+  if (!smp) {
+    pl->smp = bmpc_obstacle_sampling{};
+    return 0;
+  }
+  const Plan& P = pl->hp.plan;
+  if (smp->mode != BMPC_OBS_ARGMAX && smp->mode != BMPC_OBS_SAMPLE_MODEL)
+    return fail(-22, "bmpc_set_obstacle_sampling: unknown mode (BMPC_OBS_ARGMAX or BMPC_OBS_SAMPLE_MODEL)");
+  if (smp->hold < 1) return fail(-22, "bmpc_set_obstacle_sampling: hold must be at least 1");
+  if (smp->ego_base < 0) return fail(-22, "bmpc_set_obstacle_sampling: ego_base must not be negative");
+  if (P.desc.model == BMPC_MODEL_HIGHWAY_MERGE)
+    return fail(-22, "bmpc_set_obstacle_sampling: the merge scene's obstacle never chooses (always backup 0)");
+  if (P.desc.flags & BMPC_PLAN_TRANSFORM)
+    return fail(-22, "bmpc_set_obstacle_sampling: no closed loop runs on a plan with BMPC_PLAN_TRANSFORM");
+  if (P.desc.model == BMPC_MODEL_QUADRUPED) {
+    if (const std::string e = check_quad_scene_plan(P); !e.empty())
+      return fail(-22, "bmpc_set_obstacle_sampling: " + e);
+  } else if (P.desc.model != BMPC_MODEL_HIGHWAY || P.n != 4 || P.d != 2) {
+    return fail(-22, "bmpc_set_obstacle_sampling: the overtake scene needs a highway plan (n = 4, d = 2)");
+  }
+  pl->smp = *smp;
   return 0;
 }
 

@@ -7,6 +7,8 @@
 // a lane needs no graph, no tape and no global memory.
 #pragma once
 
+#include <type_traits>
+
 #include "bmpc_core.h"
 
 namespace bmpc {
@@ -299,7 +301,9 @@ struct Highway {
     S ex = dexp(dx), ey = dexp(dy);
     return (dx * ex + dy * ey) / (ex + ey);
   }
-  template <class S>
+  // (S a dual number; for S = double, the sampled obstacle's plain evaluation, the overload above
+  // is the same function and the only candidate)
+  template <class S, class = typename std::enable_if<!std::is_same<S, double>::value>::type>
   BMPC_HD static S veh_col(const S& a0, const S& a1, const S& b0, const S& b1, double s0, double s1) {
     S dx = dfabs(a0 - b0) - s0;
     S dy = dfabs(a1 - b1) - s1;

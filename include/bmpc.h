@@ -32,6 +32,8 @@
  *   bmpc_merge_env_step<- Highway_env_merge.step + the same collision rule
  *                                                          Highway_env_branch.py:317-380,421-429
  *   bmpc_quad_env_step <- Quad_env.step                    quadruped_env.py:67-130
+ *   bmpc_set_obstacle_sampling   (an extension: the scenes' obstacle draws its backup policy from
+ *                         branch_eval's distribution instead of the reference's argmax rules)
  *
  * Conventions: all host buffers are caller-owned, C-contiguous, ego-major, float64
  * (int32 for status/iteration counts).  Return codes are 0 on success and a negative
@@ -460,6 +462,48 @@ typedef struct {
  * message for capacity < 1, a NULL core column, or zpred on a BMPC_CTRL_ROBUST plan (its tree
  * keeps no obstacle prediction per state node). */
 int bmpc_set_loop_record(bmpc_plan* plan, const bmpc_loop_record* rec);
+
+/* The obstacle's backup choice in the device closed loops.  The reference's scenes are
+ * deterministic: the overtake obstacle takes the first argmax of a safety value
+ * (Highway_env_branch.py:137-149), the quadruped obstacle keeps backup 0 while it is clear, else
+ * the argmax (quadruped_env.py:92-101) -- BMPC_OBS_ARGMAX, what every plan does until a sampler is
+ * attached.  BMPC_OBS_SAMPLE_MODEL draws the choice from the distribution the controllers plan
+ * against, branch_eval's p_j(x, z) = prob_weight(bf_traj_j) / sum (highway_branch_dyn.py:298-301,
+ * :355-359) at the step's pre-step state with the policies in force before the step's lane-change
+ * re-targeting, so that a Monte-Carlo population shows a controller the less likely branches too.
+ * An extension: the reference has no sampled obstacle.
+ *
+ * One draw per (ego, epoch), addressed and never consumed: Philox4x32-10 (csrc/bmpc_rng.h) at
+ *   counter = {lo32(g), hi32(g), epoch, purpose},  key = {lo32(seed), hi32(seed)},
+ * g = ego_base + e the ego's global index, epoch = t / hold, purpose 0 = the obstacle's policy
+ * (other values reserved), u = ((o0 >> 5) 2^26 + (o1 >> 6)) / 2^53 in [0, 1).  The choice is the
+ * smallest j with u < p_0 + ... + p_j (m - 1 if none), taken at t % hold == 0 and kept, in the scene
+ * row's slot 13, for the epoch's other steps.  The launch path, the split of a loop over calls and
+ * the shard an ego lives in (ego_base = the shard's first global ego) cannot change a draw;
+ * bmpc/rng.py restates it in NumPy. */
+enum { BMPC_OBS_ARGMAX = 0, BMPC_OBS_SAMPLE_MODEL = 1 };
+typedef struct {
+  int32_t  mode;      /* BMPC_OBS_*                                           */
+  int32_t  hold;      /* >= 1: closed-loop steps a sampled choice is kept     */
+  uint64_t seed;
+  int64_t  ego_base;  /* >= 0: global index of the plan's ego 0 (its shard's lo) */
+} bmpc_obstacle_sampling;
+#ifdef __cplusplus
+static_assert(sizeof(bmpc_obstacle_sampling) == 24,
+              "bmpc_obstacle_sampling is 24 bytes: mode 0, hold 4, seed 8, ego_base 16");
+#endif
+
+/* Attach (copy of *s kept with the plan) or detach (s == NULL: BMPC_OBS_ARGMAX) the obstacle
+ * sampler of the plan's overtake or quadruped scene.  Host state only, like bmpc_set_loop_record:
+ * nothing is enqueued, and a loop already launched keeps the sampler it was launched with.  While
+ * attached, bmpc_loop_device / bmpc_quad_loop_device on either launch path and the single-step
+ * bmpc_env_step / bmpc_quad_env_step all obey it (unlike the recorder it changes what a step
+ * computes, so a manual loop gets the same bits).  A sampler attached mid-episode, at a t with
+ * t % hold != 0, keeps the scene row's last choice until the next epoch boundary.  With mode
+ * BMPC_OBS_ARGMAX or nothing attached every path computes the bits it computed without this entry.
+ * -22 with a message for an unknown mode, hold < 1, ego_base < 0, a HIGHWAY_MERGE plan (the merge
+ * scene's obstacle never chooses), a plan with BMPC_PLAN_TRANSFORM, or a CVaR quadruped plan. */
+int bmpc_set_obstacle_sampling(bmpc_plan* plan, const bmpc_obstacle_sampling* s);
 
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of

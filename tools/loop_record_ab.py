@@ -53,8 +53,9 @@ class Libraries:
         plan._CTX = self.ctx[name]
 
 
-def run(shape, egos, steps, warmup, seed, record):
-    """One repetition: a fresh plan, `warmup` steps, then `steps` timed ones.  record: None, "core", "full"."""
+def run(shape, egos, steps, warmup, seed, record, obstacle=None):
+    """One repetition: a fresh plan, `warmup` steps, then `steps` timed ones.  record: None, "core", "full";
+    obstacle: None or the keyword arguments of BatchPlan.set_obstacle_sampling (tools/obstacle_sampling_ab.py)."""
     import torch
     dev = torch.device("cuda", 0)
     f64 = dict(dtype=torch.float64, device=dev)
@@ -80,6 +81,8 @@ def run(shape, egos, steps, warmup, seed, record):
     st, it = (torch.zeros(egos, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.zeros((egos, abi.ENV_NSTAT), **f64)
     tx, tz, tr = (torch.zeros((egos, n), **f64) for _ in range(3))
+    if obstacle:
+        pl.set_obstacle_sampling(**obstacle)
     rec = None
     if record:
         rec = pl.new_loop_record(warmup + steps, 0, predictions=(record == "full"))
