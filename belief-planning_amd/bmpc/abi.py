@@ -52,6 +52,7 @@ class PlanDesc(C.Structure):
 ENV_STRIDE, ENV_NSTAT = 16, 8
 # scene state / statistics slots (bmpc_env.h)
 ENV_X, ENV_Z, ENV_UOBS, ENV_LANE0, ENV_LANE1, ENV_COLL, ENV_OBSPOL, ENV_STEPS = 0, 4, 8, 10, 11, 12, 13, 14
+ENV_LOGW = 15   # overtake and quadruped scenes: the running log-weight of OBS_SAMPLE_TILTED / OBS_SCRIPT (BMPC_ENV_LOGW)
 ENVS_J, ENVS_J2, ENVS_INFEAS, ENVS_ITERS, ENVS_SOLVES, ENVS_COLL_STEPS, ENVS_COLLIDED = range(7)
 
 
@@ -117,7 +118,8 @@ class LoopRecord(C.Structure):
 
 
 OBS_ARGMAX, OBS_SAMPLE_MODEL = 0, 1   # bmpc_obstacle_sampling.mode (include/bmpc.h BMPC_OBS_*)
-OBS_MODES = {"argmax": OBS_ARGMAX, "model": OBS_SAMPLE_MODEL}
+OBS_SAMPLE_TILTED, OBS_SCRIPT = 2, 3   # ... the two modes that need a proposal (bmpc_set_obstacle_proposal)
+OBS_MODES = {"argmax": OBS_ARGMAX, "model": OBS_SAMPLE_MODEL, "tilted": OBS_SAMPLE_TILTED, "script": OBS_SCRIPT}
 
 
 class ObstacleSampling(C.Structure):
@@ -127,15 +129,17 @@ class ObstacleSampling(C.Structure):
 
 
 def make_obstacle_sampling(mode="model", seed=0, hold=1, ego_base=0):
-    """Validated bmpc_obstacle_sampling: mode "argmax" / "model" (or abi.OBS_*), a seed of 64 bits,
+    """Validated bmpc_obstacle_sampling: mode "argmax" / "model" / "tilted" / "script" (or abi.OBS_*;
+    the last two need a proposal on the plan, make_obstacle_proposal), a seed of 64 bits,
     hold >= 1 closed-loop steps per sampled choice, ego_base >= 0 the global index of the plan's
     ego 0 (a shard's first ego)."""
     if isinstance(mode, str):
         if mode not in OBS_MODES:
             raise ValueError(f"obstacle sampling mode {mode!r}: one of {sorted(OBS_MODES)}")
         mode = OBS_MODES[mode]
-    if int(mode) not in (OBS_ARGMAX, OBS_SAMPLE_MODEL):
-        raise ValueError(f"obstacle sampling mode {mode!r}: abi.OBS_ARGMAX or abi.OBS_SAMPLE_MODEL")
+    if int(mode) not in OBS_MODES.values():
+        raise ValueError(f"obstacle sampling mode {mode!r}: one of abi.OBS_ARGMAX, OBS_SAMPLE_MODEL, OBS_SAMPLE_TILTED, "
+                         "OBS_SCRIPT")
     if int(hold) != hold or not 1 <= int(hold) < 2 ** 31:
         raise ValueError("hold must be an integer of at least 1")
     if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
@@ -145,6 +149,46 @@ def make_obstacle_sampling(mode="model", seed=0, hold=1, ego_base=0):
     S = ObstacleSampling()
     S.mode, S.hold, S.seed, S.ego_base = int(mode), int(hold), int(seed), int(ego_base)
     return S
+
+
+class ObstacleProposal(C.Structure):
+    """bmpc_obstacle_proposal: what modes OBS_SAMPLE_TILTED and OBS_SCRIPT choose by
+    (bmpc_set_obstacle_proposal) -- a positive tilt per policy and a device table of prescribed choices
+    int32 [batch][script_epochs] whose column 0 is epoch `epoch0`."""
+    _fields_ = [("tilt", C.c_double * MAX_M), ("script", C.c_void_p), ("script_epochs", C.c_int32),
+                ("epoch0", C.c_int32)]
+
+
+def make_obstacle_proposal(tilt=None, script=None, epoch0=0, m=None):
+    """Validated bmpc_obstacle_proposal.  tilt: m positive finite numbers b_j (None: all 1), the
+    tilted mode draws policy j with probability p_j b_j / sum_k p_k b_k; m: the plan's policy count
+    (default len(tilt), MAX_M without a tilt) -- entries beyond it are 1.  script: None, or
+    (device pointer, epochs) of a C-contiguous int32 table [batch][epochs] the caller keeps alive
+    (BatchPlan.set_obstacle_proposal uploads one from an array); epoch0 >= 0: the epoch of its
+    column 0."""
+    P = ObstacleProposal()
+    if tilt is None:
+        b = np.ones(MAX_M if m is None else int(m))
+    else:
+        b = np.asarray(tilt, dtype=np.float64)
+    if b.ndim != 1 or not 1 <= b.size <= MAX_M or (m is not None and b.size != int(m)):
+        raise ValueError(f"tilt must hold one entry per policy ({'1..%d' % MAX_M if m is None else int(m)}), "
+                         f"got shape {b.shape}")
+    if not (np.all(np.isfinite(b)) and np.all(b > 0)):
+        raise ValueError("every tilt entry must be finite and > 0")
+    for j in range(MAX_M):
+        P.tilt[j] = float(b[j]) if j < b.size else 1.0
+    if int(epoch0) != epoch0 or not 0 <= int(epoch0) < 2 ** 31:
+        raise ValueError("epoch0 must be an integer of at least 0")
+    P.epoch0 = int(epoch0)
+    if script is not None:
+        ptr, epochs = script
+        if int(epochs) != epochs or not 1 <= int(epochs) < 2 ** 31:
+            raise ValueError("a script needs at least one epoch (column)")
+        if not ptr:
+            raise ValueError("a script needs a device table")
+        P.script, P.script_epochs = int(ptr), int(epochs)
+    return P
 
 
 def _fill(arr, values):

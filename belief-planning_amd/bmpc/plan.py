@@ -107,6 +107,12 @@ class LoopRecording:
         return self._scene(abi.ENV_OBSPOL)
 
     @property
+    def logw(self):
+        """The running log-weight after each step (modes "tilted" and "script"; 0 or the caller's
+        value otherwise)."""
+        return self._scene(abi.ENV_LOGW, kinds=("overtake", "quadruped"))
+
+    @property
     def collided(self):
         return self._scene(abi.ENV_COLL)
 
@@ -294,6 +300,48 @@ class BatchPlan:
         check(lib().bmpc_set_obstacle_sampling(self._h, None if struct is None else C.byref(struct)),
               "bmpc_set_obstacle_sampling")
         self.obstacle_sampling = struct
+
+    def set_obstacle_proposal(self, tilt=None, script=None, epoch0=0):
+        """What set_obstacle_sampling's modes "tilted" and "script" choose by
+        (bmpc_set_obstacle_proposal); attach it before selecting either mode.
+
+        tilt: one positive finite b_j per policy (None: all 1).  Mode "tilted" draws, at the draw and
+        the epochs of mode "model", policy j with probability q_j = p_j b_j / sum_k p_k b_k and adds
+        log(p_j / q_j) to the scene row's slot abi.ENV_LOGW: exp of it is the episode's likelihood
+        ratio (montecarlo.estimate).  script: an integer array [batch, E] (NumPy or torch) of
+        prescribed choices in [0, m), row e for the plan's ego e, column c for epoch epoch0 + c;
+        it is checked here, uploaded as int32 and kept alive by the plan.  Mode "script" takes the
+        choice of epoch t // hold from it, makes no draw, and adds log p_j -- the model's own
+        probability of the prescribed choice -- to abi.ENV_LOGW.  Every entry point that steps a
+        scene refuses steps whose epochs the script does not cover.  The caller zeroes the slot to
+        start an estimate.  tilt=None, script=None detaches (refused while the sampler's mode is
+        "tilted" or "script").  Also takes an abi.ObstacleProposal as `tilt`."""
+        keep = None
+        if isinstance(tilt, abi.ObstacleProposal):
+            struct = tilt
+        elif tilt is None and script is None:
+            struct = None
+        else:
+            m = int(self.desc.m)
+            table = None
+            if script is not None:
+                host = script.detach().cpu().numpy() if hasattr(script, "detach") else np.asarray(script)
+                if host.dtype.kind not in "iu":
+                    raise ValueError("the script must hold integers")
+                if host.ndim != 2 or host.shape[0] != self.batch or host.shape[1] < 1:
+                    raise ValueError(f"the script must have shape [batch = {self.batch}, epochs >= 1], got {host.shape}")
+                if host.min() < 0 or host.max() >= m:
+                    raise ValueError(f"script entries must lie in [0, {m})")
+                table = (np.ascontiguousarray(host, np.int32), host.shape[1])
+            struct = abi.make_obstacle_proposal(tilt, None, epoch0, m=m)
+            if table is not None:
+                import torch
+                keep = torch.tensor(table[0], dtype=torch.int32, device=torch.device("cuda", self.device))
+                torch.cuda.synchronize(keep.device)
+                struct.script, struct.script_epochs = keep.data_ptr(), table[1]
+        check(lib().bmpc_set_obstacle_proposal(self._h, None if struct is None else C.byref(struct)),
+              "bmpc_set_obstacle_proposal")
+        self.obstacle_proposal, self._script = struct, keep
 
     def new_loop_record(self, capacity, t_base=0, predictions=False, device=None):
         """A LoopRecording of `capacity` rows per ego from closed-loop step `t_base` on, in fresh

@@ -128,13 +128,20 @@ def sampled_overtake_population(B, steps, seed=0, device=0, record=False, obstac
     ego then has the trajectory it has in the unsharded run.  desc: another highway plan description
     than highway_desc().  Any draw can be audited on the host with bmpc.rng.obstacle_uniform(
     obstacle_seed, global ego, t // hold)."""
-    import torch
     from . import plan
     total, rows = _shard_rows(B, ego_base, population)
     x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
     pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
     pl.set_policies(highway_policy_rows(tgt))
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    return _overtake_loop(pl, x, z, steps, record, device)
+
+
+def _overtake_loop(pl, x, z, steps, record, device):
+    """`steps` closed-loop steps from t = 0 of the overtake plan `pl` (policies and obstacle rule set)
+    from the states x, z [B, 4]: the population entries' results; closes the plan."""
+    import torch
+    B = pl.batch
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
     scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
@@ -300,16 +307,24 @@ def sampled_quadruped_population(B, steps, seed=0, device=0, record=False, obsta
     """quadruped_population with the sampled obstacle: sampled_overtake_population's arguments and
     sharding rule (rows ego_base .. ego_base + B - 1 of seeded_quadruped_batch(population, seed) and
     of seeded_quadruped_goals; a sharded run passes ego_base = distributed.shard(...)[0])."""
-    import torch
     from . import plan
     total, rows = _shard_rows(B, ego_base, population)
     x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
     pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
     pl.set_policies(quadruped_policy_rows(B))
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    return _quadruped_loop(pl, quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), steps, record, device)
+
+
+def _quadruped_loop(pl, scene0, steps, record, device):
+    """`steps` closed-loop steps from t = 0 of the quadruped plan `pl` (policies and obstacle rule set)
+    from the scene rows scene0 [B, ENV_STRIDE] (quad_scene): the population entries' results; closes
+    the plan."""
+    import torch
+    B = pl.batch
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
-    scene = torch.tensor(quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), **f64)
+    scene = torch.tensor(scene0, **f64)
     up = torch.zeros((B, pl.U, 3), **f64)
     J = torch.zeros(B, **f64)
     st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
@@ -326,6 +341,96 @@ def sampled_quadruped_population(B, steps, seed=0, device=0, record=False, obsta
         out += (rec.host(),)
     pl.close()
     return out
+
+
+def _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base):
+    """The tilted obstacle of a weighted_*_population call: the proposal, then the mode that needs it."""
+    pl.set_obstacle_proposal(tilt=tilt)
+    pl.set_obstacle_sampling("tilted", seed=obstacle_seed, hold=hold, ego_base=ego_base)
+
+
+def _attach_script(pl, m, epochs, hold):
+    """The full enumeration of an enumerated_*_population call: ego e follows row e of
+    montecarlo.enumerate_scripts(m, epochs), one choice per `hold` steps."""
+    from . import montecarlo
+    if pl.batch != m ** epochs:
+        raise ValueError(f"the plan must hold {m} ** {epochs} egos, one per path")
+    script = montecarlo.enumerate_scripts(m, epochs)
+    pl.set_obstacle_proposal(script=script)
+    pl.set_obstacle_sampling("script", hold=hold)
+    return script
+
+
+def _with_logw(out):
+    """(stats, scene[, record]) -> (stats, scene, logw[, record]): the scenes' ENV_LOGW column."""
+    return out[:2] + (out[1][:, abi.ENV_LOGW].copy(),) + out[2:]
+
+
+def weighted_overtake_population(B, steps, seed=0, device=0, record=False, obstacle_seed=0, hold=1, ego_base=0,
+                                 population=None, desc=None, tilt=None):
+    """sampled_overtake_population under importance sampling: the obstacle draws from the model's
+    branch distribution tilted by `tilt` (one positive b_j per policy, None: all 1 -- the sampled
+    population itself; BatchPlan.set_obstacle_proposal, mode "tilted"), at the same draws and with the
+    same sharding rule (ego_base = distributed.shard(...)[0]).  Returns the statistics rows, the final
+    scene and the per-ego log-weight logw [B] = log of the likelihood ratio p / q of each ego's
+    realised choice sequence (the scene's abi.ENV_LOGW column, which starts at 0); with `record` also
+    the record, whose `logw` column holds the weight's history.  montecarlo.estimate(f, logw) is the
+    estimate of E_p[f] with its standard error."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
+    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
+    pl.set_policies(highway_policy_rows(tgt))
+    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
+    return _with_logw(_overtake_loop(pl, x, z, steps, record, device))
+
+
+def weighted_quadruped_population(B, steps, seed=0, device=0, record=False, obstacle_seed=0, hold=1, ego_base=0,
+                                  population=None, desc=None, tilt=None):
+    """sampled_quadruped_population under importance sampling: weighted_overtake_population's
+    arguments and results (sharding by ego_base = distributed.shard(...)[0])."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
+    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
+    pl.set_policies(quadruped_policy_rows(B))
+    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
+    scene0 = quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows])
+    return _with_logw(_quadruped_loop(pl, scene0, steps, record, device))
+
+
+def enumerated_overtake_population(x0, z0, epochs, hold, device=0, record=False, desc=None):
+    """One initial state (x0, z0) against every obstacle choice sequence of `epochs` epochs of `hold`
+    steps: m ** epochs egos, ego e following row e of montecarlo.enumerate_scripts(m, epochs)
+    (BatchPlan.set_obstacle_proposal, mode "script"), for epochs * hold closed-loop steps.  Returns
+    the statistics rows, the final scene, the path log-probabilities logp [m ** epochs] under the
+    model's branch distribution (they sum to one: montecarlo.exact_expectation gives exact closed-loop
+    expectations over the scenario tree) and the script; with `record` also the record."""
+    from . import plan
+    desc = highway_desc() if desc is None else desc
+    B = int(desc.m) ** int(epochs)
+    x = np.tile(np.asarray(x0, float).reshape(1, 4), (B, 1))
+    z = np.tile(np.asarray(z0, float).reshape(1, 4), (B, 1))
+    pl = plan.BatchPlan(desc, B, device)
+    pl.set_policies(highway_policy_rows(xref_rule(x, z)[1]))
+    script = _attach_script(pl, int(desc.m), int(epochs), hold)
+    out = _with_logw(_overtake_loop(pl, x, z, int(epochs) * int(hold), record, device))
+    return out[:3] + (script,) + out[3:]
+
+
+def enumerated_quadruped_population(x0, z0, x_des, epochs, hold, device=0, record=False, desc=None):
+    """enumerated_overtake_population for the quadruped scene: one initial state (x0, z0 [3]) and goal
+    x_des [3] against all m ** epochs choice sequences."""
+    from . import plan
+    desc = quadruped_desc() if desc is None else desc
+    B = int(desc.m) ** int(epochs)
+    x = np.tile(np.asarray(x0, float).reshape(1, 3), (B, 1))
+    pl = plan.BatchPlan(desc, B, device)
+    pl.set_policies(quadruped_policy_rows(B))
+    script = _attach_script(pl, int(desc.m), int(epochs), hold)
+    scene0 = quad_scene(x, np.asarray(z0, float).reshape(1, 3), np.asarray(x_des, float).reshape(1, 3))
+    out = _with_logw(_quadruped_loop(pl, scene0, int(epochs) * int(hold), record, device))
+    return out[:3] + (script,) + out[3:]
 
 
 def quadruped_xref(x, x_des=(5.0, -3.0, 0.0)):

@@ -406,14 +406,17 @@ __device__ __attribute__((noinline)) IpmResult loop_ipm(const X ex, const Plan& 
 }
 // (smp: the plan's obstacle sampler, bmpc_set_obstacle_sampling, by reference out of the kernel
 // argument like env -- two argument registers; the sampled rule lives in here, on lane 0, under a
-// branch on its mode, so the solve's register budget never sees it.  e: the wave's ego.)
+// branch on its mode, so the solve's register budget never sees it.  e: the wave's ego.  prop: the
+// plan's device copy of its obstacle proposal, bmpc_set_obstacle_proposal, or null -- one pointer,
+// read by the weighted modes only.)
 __device__ __attribute__((noinline)) void loop_env_step(const bmpc_env_desc& env, double dt, int N, int m, int t,
                                                         double* st, bmpc_policy* pol, const double* up, double* x,
                                                         double* z, double* xr, double Jv, int status, int iters,
                                                         double* stats, const bmpc_obstacle_sampling& smp,
-                                                        const double* mc, int e) {
+                                                        const double* mc, int e,
+                                                        const bmpc_obstacle_proposal* prop) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, true, stats);
-  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e);
+  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, prop);
 }
 
 // One merge-scene step of one ego into its slab (k_env_merge and the merge k_loop): the scene
@@ -446,9 +449,10 @@ __device__ __attribute__((noinline)) void loop_quad_env_step(const bmpc_quad_env
                                                              double* st, const bmpc_policy* pol, const double* up,
                                                              double* x, double* z, double* xr, double Jv, int status,
                                                              int iters, double* stats,
-                                                             const bmpc_obstacle_sampling& smp, int e) {
+                                                             const bmpc_obstacle_sampling& smp, int e,
+                                                             const bmpc_obstacle_proposal* prop) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, false, stats);
-  quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr, &smp, e);
+  quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr, &smp, e, prop);
 }
 
 // Ego e's row r of the closed loops' recorder (bmpc_record.h), by the 64 lanes of one wave: the
@@ -493,7 +497,8 @@ __device__ __attribute__((noinline)) void loop_record_wide(double* upred, double
 // The scene of a k_loop (its kernel argument): one ego's scene step on lane 0, through an
 // out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
 // ego's transform slots, the quadruped scene neither.  The overtake and the quadruped scene carry the
-// plan's obstacle sampler (mode 0: none); the merge scene's obstacle never chooses.  kQp: the step's
+// plan's obstacle sampler (mode 0: none) and a pointer to its proposal (null: none); the merge scene's
+// obstacle never chooses.  kQp: the step's
 // solve is the OSQP-class controllers' solve_ego_qp (k_qp's) instead of the CVaR IPM.  kInlineIpm: the solve inlined into
 // the kernel as k_ipm / k_qp have it (the tree and scene steps stay calls) instead of a call of
 // its own -- as a callee the IPM's frame grows from k_ipm's ~590 to ~1,490 bytes per lane (merge
@@ -504,10 +509,11 @@ struct OvertakeScene {
   static constexpr bool kInlineIpm = false;
   bmpc_env_desc env;
   bmpc_obstacle_sampling smp;
+  const bmpc_obstacle_proposal* prop;
   __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
     loop_env_step(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, P.desc.mc,
-                  (int)blockIdx.x);
+                  (int)blockIdx.x, prop);
   }
 };
 struct MergeScene {
@@ -525,9 +531,10 @@ struct QuadScene {
   static constexpr bool kInlineIpm = BMPC_QUAD_LOOP_INLINE_QP != 0;   // (both forms measured)
   bmpc_quad_env_desc env;
   bmpc_obstacle_sampling smp;
+  const bmpc_obstacle_proposal* prop;
   __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
-    loop_quad_env_step(env, P, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, (int)blockIdx.x);
+    loop_quad_env_step(env, P, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, (int)blockIdx.x, prop);
   }
 };
 
@@ -628,6 +635,7 @@ struct SolveLaunch {
   const struct PhasedLaunch* ph = nullptr;   // tools-only builds (BMPC_WITH_PHASED, below)
   bmpc_loop_record rec = {};         // the fused closed loop's recorder (capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the fused closed loop's obstacle sampler (mode 0: none)
+  const bmpc_obstacle_proposal* prop = nullptr;   // ... and the plan's device copy of its proposal (null: none)
 };
 using LaunchFn = hipError_t(const SolveLaunch&);
 

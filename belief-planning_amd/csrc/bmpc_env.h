@@ -31,6 +31,7 @@ enum {
   ENV_COLL = 12,    // Highway_sim collision flag (sticky)
   ENV_OBSPOL = 13,  // obstacle backup index chosen by the last pre()
   ENV_STEPS = 14,   // control steps taken
+  ENV_LOGW = BMPC_ENV_LOGW,   // running log-weight of the weighted obstacle modes (also the quadruped scene's)
   ENV_STRIDE = BMPC_ENV_STRIDE
 };
 
@@ -77,25 +78,60 @@ BMPC_HD void env_policy_u(int kind, const double* x, double Kpsi, const double* 
 // doubles, no Jacobian -- at the draw of (seed, ego_base + e, t / hold); otherwise `prev`, the scene
 // row's choice of the step before (clamped to a policy: a sampler attached mid-episode, or a row
 // the caller wrote, keeps it until the next epoch boundary).  mc: the plan's model constants.
+//
+// The weighted modes (bmpc_set_obstacle_proposal; Q the plan's proposal, logw the scene row's
+// ENV_LOGW slot) choose at the same epoch starts from the same weights w_j and add the log-weight of
+// their choice to *logw; inside an epoch they too return `prev` and leave *logw alone.
+//   BMPC_OBS_SAMPLE_TILTED: the inverse CDF of w_j b_j (b = Q->tilt) at the same draw, and
+//     log((sum w_k b_k) / (b_j sum w_k)) = log(p_j / q_j) -- with b == 1 the products are the w_j
+//     themselves, so the choice is the untilted one and the quotient is exactly 1: + 0.0;
+//   BMPC_OBS_SCRIPT: Q->script[e][t / hold - epoch0] clamped to a policy, no draw, and
+//     log(w_j / sum w_k) = log p_j.  (The entry points check on the host that the script covers
+//     the epochs of their steps; the column is clamped here all the same, so that a table is never
+//     read outside its rows.)
+// All sums run in the order k = 0, 1, ...
 template <class M>
 BMPC_HD int env_sampled_choice(const bmpc_obstacle_sampling& S, long long e, const double* mc, double dt, int N,
-                               int m, int t, const bmpc_policy* pol, const double* x, const double* z, double prev) {
+                               int m, int t, const bmpc_policy* pol, const double* x, const double* z, double prev,
+                               const bmpc_obstacle_proposal* Q = nullptr, double* logw = nullptr) {
   if (t % S.hold != 0) return prev >= (double)(m - 1) ? m - 1 : prev > 0.0 ? (int)prev : 0;
   double w[BMPC_MAX_M];
   for (int j = 0; j < m; ++j) w[j] = M::prob_weight(mc, M::bf_traj(mc, dt, N, pol[0], pol[j], x, z));
-  return rng_inverse_cdf(w, m, obstacle_uniform(S.seed, (uint64_t)(S.ego_base + e), (uint32_t)(t / S.hold)));
+  if (S.mode == BMPC_OBS_SCRIPT) {
+    int c = t / S.hold - Q->epoch0;
+    c = c >= Q->script_epochs ? Q->script_epochs - 1 : c > 0 ? c : 0;
+    int j = Q->script[(size_t)e * (size_t)Q->script_epochs + (size_t)c];
+    j = j >= m - 1 ? m - 1 : j > 0 ? j : 0;
+    double sw = 0.0;
+    for (int k = 0; k < m; ++k) sw += w[k];
+    *logw += log(w[j] / sw);
+    return j;
+  }
+  const double u = obstacle_uniform(S.seed, (uint64_t)(S.ego_base + e), (uint32_t)(t / S.hold));
+  if (S.mode != BMPC_OBS_SAMPLE_TILTED) return rng_inverse_cdf(w, m, u);
+  double wb[BMPC_MAX_M], sw = 0.0, swb = 0.0;
+  {
+#pragma clang fp contract(off)   // (w_k b_k rounded before it is added, in every kernel that inlines this)
+    for (int k = 0; k < m; ++k) wb[k] = w[k] * Q->tilt[k];
+    for (int k = 0; k < m; ++k) sw += w[k], swb += wb[k];
+  }
+  const int j = rng_inverse_cdf(wb, m, u);
+  *logw += log(swb / (Q->tilt[j] * sw));
+  return j;
 }
-BMPC_HD bool env_samples(const bmpc_obstacle_sampling* smp) { return smp && smp->mode == BMPC_OBS_SAMPLE_MODEL; }
+BMPC_HD bool env_samples(const bmpc_obstacle_sampling* smp) { return smp && smp->mode != BMPC_OBS_ARGMAX; }
 
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; pol: the
 // ego's m model policies (the lane-change target is re-targeted in place, update_backup);
 // u0: uPred[0] of the last solve (unused at t == 0); x_out, z_out, xref_out: the next
 // solve's inputs.  smp: the plan's obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the
-// reference's argmax rule), with mc, the plan's model constants, and e, the ego's index in the plan.
+// reference's argmax rule), with mc, the plan's model constants, and e, the ego's index in the plan;
+// prop: the plan's obstacle proposal (read in modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT only).
 BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t, double* st,
                           bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
                           double* xref_out, const bmpc_obstacle_sampling* smp = nullptr,
-                          const double* mc = nullptr, long long e = 0) {
+                          const double* mc = nullptr, long long e = 0,
+                          const bmpc_obstacle_proposal* prop = nullptr) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
@@ -111,7 +147,7 @@ BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t
   }
   int best = 0;
   if (env_samples(smp)) {   // (the policies in force before this step's re-targeting below)
-    best = env_sampled_choice<Highway>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL]);
+    best = env_sampled_choice<Highway>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL], prop, st + ENV_LOGW);
   } else {
     // safety value of every obstacle backup against the ego's backup-0 rollout (the ego's
     // backupidx is never changed): min over the rows of veh_col and lane_bdry_h of the ego

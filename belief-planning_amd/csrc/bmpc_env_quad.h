@@ -42,10 +42,11 @@ BMPC_HD double quad_env_robot_col(const double* mc, double a0, double a1, double
 // model constants; pol: the ego's m model policies; u0: uPred[0] of the last solve (unused at
 // t == 0); x_out, z_out, xref_out: the next solve's inputs (3 doubles each).  smp: the plan's
 // obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the reference's rule); e: the ego's
-// index in the plan.
+// index in the plan; prop: the plan's obstacle proposal (the weighted modes, bmpc_env.h).
 BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, double dt, int N, int m, int t,
                                double* st, const bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
-                               double* xref_out, const bmpc_obstacle_sampling* smp = nullptr, long long e = 0) {
+                               double* xref_out, const bmpc_obstacle_sampling* smp = nullptr, long long e = 0,
+                               const bmpc_obstacle_proposal* prop = nullptr) {
   double* x = st + QENV_X;
   double* z = st + QENV_Z;
   if (t > 0) {   // post(t-1): robot.step of ego and obstacle
@@ -57,7 +58,7 @@ BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, do
   }
   int best = 0;
   if (env_samples(smp)) {
-    best = env_sampled_choice<Quadruped>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL]);
+    best = env_sampled_choice<Quadruped>(*smp, e, mc, dt, N, m, t, pol, x, z, st[ENV_OBSPOL], prop, st + ENV_LOGW);
   } else {
     // clearance of every obstacle backup against the ego's policy-0 rollout (the ego's backupidx
     // is never changed): the rollouts of zpred_eval, row by row (rollout<> of one step, in place)

@@ -36,18 +36,19 @@ static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, s
 }
 
 // one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve.  smp: the plan's
-// obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device
+// obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device, prop: the
+// plan's device copy of its obstacle proposal (null: none; read by the weighted modes only)
 __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, int t, int batch, double* scene,
                       bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
                       const int32_t* iters, int cvar, double* x, double* z, double* xref, double* stats,
-                      bmpc_obstacle_sampling smp, const double* mc) {
+                      bmpc_obstacle_sampling smp, const double* mc, const bmpc_obstacle_proposal* prop) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   double* st = scene + (size_t)e * ENV_STRIDE;
   if (t > 0 && stats && J && status && iters)
     env_accumulate(st, J[e], status[e], iters[e], cvar != 0, stats + (size_t)e * ENVS_STRIDE);
   env_step_ego(E, dt, N, m, t, st, pol + (size_t)e * m, upred ? upred + (size_t)e * U * d : nullptr,
-               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e);
+               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e, prop);
 }
 
 // one thread per ego: the merge scene step (bmpc_env_merge.h) around the solve; S, bx and their
@@ -71,7 +72,7 @@ __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E,
 __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, int t, int batch, double* scene,
                            const bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
                            const int32_t* iters, double* x, double* z, double* xref, double* stats,
-                           bmpc_obstacle_sampling smp) {
+                           bmpc_obstacle_sampling smp, const bmpc_obstacle_proposal* prop) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   const Plan& P = B->P;
@@ -80,7 +81,7 @@ __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, i
     env_accumulate(st, J[e], status[e], iters[e], false, stats + (size_t)e * ENVS_STRIDE);
   quad_env_step_ego(E, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol + (size_t)e * P.m,
                     upred ? upred + (size_t)e * P.U * P.d : nullptr, x + (size_t)e * 3, z + (size_t)e * 3,
-                    xref + (size_t)e * 3, &smp, e);
+                    xref + (size_t)e * 3, &smp, e, prop);
 }
 
 // One wave per ego: step t's row of the closed loops' recorder after the per-step launches (run_loop)
@@ -379,6 +380,11 @@ struct bmpc_plan {
   int n_mref = 0;   // 0: no merge scene set
   bmpc_loop_record rec = {};   // the closed loops' recorder (bmpc_set_loop_record; capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the scenes' obstacle sampler (bmpc_set_obstacle_sampling; mode 0: none)
+  // the obstacle proposal (bmpc_set_obstacle_proposal): the host copy, and the device copy the scene
+  // kernels read through one pointer (allocated at the first attach; has_prop false: none attached)
+  bmpc_obstacle_proposal prop = {};
+  bmpc_obstacle_proposal* d_prop = nullptr;
+  bool has_prop = false;
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
 
@@ -394,6 +400,22 @@ static int drain(bmpc_plan* pl) {
   HIPCHECK(hipStreamSynchronize(pl->stream));
   if (pl->user_stream) HIPCHECK(hipStreamSynchronize(pl->user_stream));
   return 0;
+}
+
+// the proposal pointer the scene kernels get: the plan's device copy, or null when none is attached
+static const bmpc_obstacle_proposal* scene_proposal(const bmpc_plan* pl) { return pl->has_prop ? pl->d_prop : nullptr; }
+
+// "" when the plan's sampler is not in mode BMPC_OBS_SCRIPT or its script covers every epoch of the
+// closed-loop steps [t0, t0 + nsteps) (t0 >= 0, nsteps >= 1): checked on the host by every entry that
+// steps a scene, before anything is enqueued
+static std::string check_script_covers(const bmpc_plan* pl, int t0, int nsteps) {
+  if (pl->smp.mode != BMPC_OBS_SCRIPT) return "";
+  const long long first = t0 / pl->smp.hold, last = ((long long)t0 + nsteps - 1) / pl->smp.hold;
+  const long long lo = pl->prop.epoch0, hi = lo + pl->prop.script_epochs;
+  if (pl->has_prop && first >= lo && last < hi) return "";
+  return "the script covers epochs " + std::to_string(lo) + ".." + std::to_string(hi - 1) + ", steps " +
+         std::to_string(t0) + ".." + std::to_string((long long)t0 + nsteps - 1) + " need epochs " +
+         std::to_string(first) + ".." + std::to_string(last) + " (bmpc_set_obstacle_proposal)";
 }
 
 // the plan's constants and layout, with the table and lane-reference pointers at their device
@@ -495,6 +517,7 @@ int bmpc_plan_destroy(bmpc_plan* pl) {
   hipFree(pl->d_scratch);
   hipFree(pl->d_lref);
   hipFree(pl->d_mref);
+  hipFree(pl->d_prop);
   hipFree(pl->d_blk_lay);
   for (auto& e : pl->ev)
     if (e) hipEventDestroy(e);
@@ -814,7 +837,8 @@ extern "C++" {
 // (bmpc_set_loop_record) rides along either way: k_loop takes it as an argument; the per-step path
 // launches k_loop_record after each solve whose step lies in the window.  The plan's obstacle sampler
 // (bmpc_set_obstacle_sampling) reaches both paths: k_loop's scene argument carries it, and `step` is
-// the single-step entry point, which passes it to k_env / k_env_quad.
+// the single-step entry point, which passes it to k_env / k_env_quad; the pointer to the plan's obstacle
+// proposal (bmpc_set_obstacle_proposal) travels beside it on both.
 template <class Step, class Fused>
 static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_scene, double* d_upred,
                     double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
@@ -838,6 +862,7 @@ static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nst
   SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
   a.rec = pl->rec;
   a.smp = pl->smp;
+  a.prop = scene_proposal(pl);
   pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
   // (the whole fused launch is booked as the solver's time, none as the tree's)
   if (const int rc = timing_mark(pl, s, 0)) return rc;
@@ -897,12 +922,13 @@ int bmpc_env_step(bmpc_plan* pl, const bmpc_env_desc* env, int t, double* d_scen
     return fail(-22, "bmpc_env_step: the overtake scene needs a highway plan (n = 4, d = 2)");
   if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_env_step: t > 0 needs the last uPred");
   if (env->n_lane < 1) return fail(-22, "bmpc_env_step: n_lane < 1");
+  if (const std::string e = check_script_covers(pl, t, 1); !e.empty()) return fail(-22, "bmpc_env_step: " + e);
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env, dim3((pl->batch + 63) / 64), dim3(64), 0, s, *env, P.desc.dt, P.N, P.m, P.U, P.d, t,
                      pl->batch, d_scene, pl->d_pol, d_upred, d_J, d_status, d_iters,
                      P.desc.controller == BMPC_CTRL_CVAR ? 1 : 0, d_x, d_z, d_xref, d_stats, pl->smp,
-                     pl->d_bundle->P.desc.mc);
+                     pl->d_bundle->P.desc.mc, scene_proposal(pl));
   HIPCHECK(hipGetLastError());
   pl->pol_on_device = true;
   return 0;
@@ -920,6 +946,8 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
     return fail(-22, "bmpc_loop_device: CVaR or robust controllers only");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_loop_device: nsteps >= 1 and t0 >= 0");
   if (env->n_lane < 1) return fail(-22, "bmpc_loop_device: n_lane < 1");
+  if (const std::string e = check_script_covers(pl, t0, nsteps); !e.empty())
+    return fail(-22, "bmpc_loop_device: " + e);
   return run_loop(
       pl, true, false, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
@@ -1002,10 +1030,11 @@ int bmpc_quad_env_step(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t, doub
   const Plan& P = pl->hp.plan;
   if (const std::string e = check_quad_scene_plan(P); !e.empty()) return fail(-22, "bmpc_quad_env_step: " + e);
   if (t < 0 || (t > 0 && !d_upred)) return fail(-22, "bmpc_quad_env_step: t >= 0, and t > 0 needs the last uPred");
+  if (const std::string e = check_script_covers(pl, t, 1); !e.empty()) return fail(-22, "bmpc_quad_env_step: " + e);
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env_quad, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, *env, t, pl->batch, d_scene,
-                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, pl->smp);
+                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, pl->smp, scene_proposal(pl));
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1018,6 +1047,8 @@ int bmpc_quad_loop_device(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t0, 
   if (const std::string e = check_quad_scene_plan(pl->hp.plan); !e.empty())
     return fail(-22, "bmpc_quad_loop_device: " + e);
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_quad_loop_device: nsteps >= 1 and t0 >= 0");
+  if (const std::string e = check_script_covers(pl, t0, nsteps); !e.empty())
+    return fail(-22, "bmpc_quad_loop_device: " + e);
   return run_loop(
       pl, false, true, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
@@ -1042,6 +1073,16 @@ int bmpc_set_loop_record(bmpc_plan* pl, const bmpc_loop_record* rec) {
   return 0;
 }
 
+// "" for the plans whose scene has an obstacle that chooses: overtake and quadruped scene plans
+static std::string check_obstacle_chooses(const Plan& P) {
+  if (P.desc.model == BMPC_MODEL_HIGHWAY_MERGE) return "the merge scene's obstacle never chooses (always backup 0)";
+  if (P.desc.flags & BMPC_PLAN_TRANSFORM) return "no closed loop runs on a plan with BMPC_PLAN_TRANSFORM";
+  if (P.desc.model == BMPC_MODEL_QUADRUPED) return check_quad_scene_plan(P);
+  if (P.desc.model != BMPC_MODEL_HIGHWAY || P.n != 4 || P.d != 2)
+    return "the overtake scene needs a highway plan (n = 4, d = 2)";
+  return "";
+}
+
 int bmpc_set_obstacle_sampling(bmpc_plan* pl, const bmpc_obstacle_sampling* smp) {
   if (!pl) return fail(-22, "null argument");
   if (!smp) {
@@ -1049,21 +1090,50 @@ int bmpc_set_obstacle_sampling(bmpc_plan* pl, const bmpc_obstacle_sampling* smp)
     return 0;
   }
   const Plan& P = pl->hp.plan;
-  if (smp->mode != BMPC_OBS_ARGMAX && smp->mode != BMPC_OBS_SAMPLE_MODEL)
-    return fail(-22, "bmpc_set_obstacle_sampling: unknown mode (BMPC_OBS_ARGMAX or BMPC_OBS_SAMPLE_MODEL)");
+  if (smp->mode < BMPC_OBS_ARGMAX || smp->mode > BMPC_OBS_SCRIPT)
+    return fail(-22, "bmpc_set_obstacle_sampling: unknown mode (BMPC_OBS_ARGMAX, _SAMPLE_MODEL, _SAMPLE_TILTED or _SCRIPT)");
   if (smp->hold < 1) return fail(-22, "bmpc_set_obstacle_sampling: hold must be at least 1");
   if (smp->ego_base < 0) return fail(-22, "bmpc_set_obstacle_sampling: ego_base must not be negative");
-  if (P.desc.model == BMPC_MODEL_HIGHWAY_MERGE)
-    return fail(-22, "bmpc_set_obstacle_sampling: the merge scene's obstacle never chooses (always backup 0)");
-  if (P.desc.flags & BMPC_PLAN_TRANSFORM)
-    return fail(-22, "bmpc_set_obstacle_sampling: no closed loop runs on a plan with BMPC_PLAN_TRANSFORM");
-  if (P.desc.model == BMPC_MODEL_QUADRUPED) {
-    if (const std::string e = check_quad_scene_plan(P); !e.empty())
-      return fail(-22, "bmpc_set_obstacle_sampling: " + e);
-  } else if (P.desc.model != BMPC_MODEL_HIGHWAY || P.n != 4 || P.d != 2) {
-    return fail(-22, "bmpc_set_obstacle_sampling: the overtake scene needs a highway plan (n = 4, d = 2)");
-  }
+  if (const std::string e = check_obstacle_chooses(P); !e.empty()) return fail(-22, "bmpc_set_obstacle_sampling: " + e);
+  if (smp->mode >= BMPC_OBS_SAMPLE_TILTED && !pl->has_prop)
+    return fail(-22, "bmpc_set_obstacle_sampling: modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT need a proposal "
+                     "(bmpc_set_obstacle_proposal)");
+  if (smp->mode == BMPC_OBS_SCRIPT && pl->prop.script_epochs == 0)
+    return fail(-22, "bmpc_set_obstacle_sampling: mode BMPC_OBS_SCRIPT needs a proposal with a script");
   pl->smp = *smp;
+  return 0;
+}
+
+int bmpc_set_obstacle_proposal(bmpc_plan* pl, const bmpc_obstacle_proposal* q) {
+  if (!pl) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (!q) {
+    if (pl->smp.mode >= BMPC_OBS_SAMPLE_TILTED)
+      return fail(-22, "bmpc_set_obstacle_proposal: the sampler's mode needs the proposal: detach or change the "
+                       "sampler first (bmpc_set_obstacle_sampling)");
+    pl->has_prop = false;   // (the device copy stays allocated: a loop in flight may still read it)
+    pl->prop = bmpc_obstacle_proposal{};
+    return 0;
+  }
+  if (const std::string e = check_obstacle_chooses(P); !e.empty()) return fail(-22, "bmpc_set_obstacle_proposal: " + e);
+  for (int j = 0; j < P.m; ++j)
+    if (!(std::isfinite(q->tilt[j]) && q->tilt[j] > 0.0))
+      return fail(-22, "bmpc_set_obstacle_proposal: tilt[" + std::to_string(j) + "] must be finite and > 0");
+  if (q->script_epochs < 0) return fail(-22, "bmpc_set_obstacle_proposal: script_epochs must not be negative");
+  if (q->epoch0 < 0) return fail(-22, "bmpc_set_obstacle_proposal: epoch0 must not be negative");
+  if (q->script_epochs > 0 && !q->script)
+    return fail(-22, "bmpc_set_obstacle_proposal: script_epochs > 0 needs the device table (null script)");
+  if (pl->smp.mode == BMPC_OBS_SCRIPT && q->script_epochs == 0)
+    return fail(-22, "bmpc_set_obstacle_proposal: the sampler's mode BMPC_OBS_SCRIPT needs a proposal with a script");
+  bmpc_obstacle_proposal h = *q;
+  for (int j = P.m; j < BMPC_MAX_M; ++j) h.tilt[j] = 1.0;   // (never read)
+  if (h.script_epochs == 0) h.script = nullptr;
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  if (const int rc = drain(pl)) return rc;   // no scene step in flight reads the old copy
+  if (!pl->d_prop) HIPCHECK(hipMalloc(&pl->d_prop, sizeof(bmpc_obstacle_proposal)));
+  HIPCHECK(hipMemcpy(pl->d_prop, &h, sizeof(h), hipMemcpyHostToDevice));
+  pl->prop = h;
+  pl->has_prop = true;
   return 0;
 }
 

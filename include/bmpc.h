@@ -34,6 +34,8 @@
  *   bmpc_quad_env_step <- Quad_env.step                    quadruped_env.py:67-130
  *   bmpc_set_obstacle_sampling   (an extension: the scenes' obstacle draws its backup policy from
  *                         branch_eval's distribution instead of the reference's argmax rules)
+ *   bmpc_set_obstacle_proposal   (an extension: the draw tilted per policy, or a prescribed choice
+ *                         per ego and epoch, with a running log-weight in the scene row)
  *
  * Conventions: all host buffers are caller-owned, C-contiguous, ego-major, float64
  * (int32 for status/iteration counts).  Return codes are 0 on success and a negative
@@ -48,6 +50,7 @@
 #ifndef BMPC_H
 #define BMPC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -502,8 +505,60 @@ static_assert(sizeof(bmpc_obstacle_sampling) == 24,
  * t % hold != 0, keeps the scene row's last choice until the next epoch boundary.  With mode
  * BMPC_OBS_ARGMAX or nothing attached every path computes the bits it computed without this entry.
  * -22 with a message for an unknown mode, hold < 1, ego_base < 0, a HIGHWAY_MERGE plan (the merge
- * scene's obstacle never chooses), a plan with BMPC_PLAN_TRANSFORM, or a CVaR quadruped plan. */
+ * scene's obstacle never chooses), a plan with BMPC_PLAN_TRANSFORM, or a CVaR quadruped plan.  The
+ * modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT (below) need bmpc_set_obstacle_proposal first. */
 int bmpc_set_obstacle_sampling(bmpc_plan* plan, const bmpc_obstacle_sampling* s);
+
+/* Weighted obstacle scenarios: two more values of bmpc_obstacle_sampling.mode, both chosen by a
+ * proposal attached to the plan beforehand, and a running log-weight per ego in the overtake and
+ * quadruped scene rows' slot BMPC_ENV_LOGW (free in both layouts; the merge scene never writes it):
+ *
+ *   scene [batch][BMPC_ENV_STRIDE], slot 15 = BMPC_ENV_LOGW: accumulated onto whatever the row
+ *   holds -- the caller zeroes it to start an estimate -- at the epoch starts (t % hold == 0) of
+ *   modes 2 and 3 only; modes 0 and 1 and a plan without a sampler never write it.
+ *
+ * BMPC_OBS_SAMPLE_TILTED (importance sampling): at an epoch start the scene forms mode 1's weights
+ * w_j (the same state, the same policies before the step's re-targeting) and draws, by the same
+ * inverse CDF at the same draw (purpose 0 at (seed, ego_base + e, t / hold)), from w_j b_j instead
+ * of w_j, b = tilt; it adds log((sum_k w_k b_k) / (b_j sum_k w_k)) = log(p_j / q_j) for the chosen j
+ * to BMPC_ENV_LOGW, both sums in the order k = 0, 1, ...  With b == 1 it computes mode 1's bits and
+ * adds exactly 0.  exp(BMPC_ENV_LOGW) is the likelihood ratio of the episode's choice sequence.
+ *
+ * BMPC_OBS_SCRIPT (prescribed choices): at an epoch start the choice of ego e is
+ * script[e][t / hold - epoch0], clamped to [0, m - 1]; no draw is made and the seed is ignored.  It
+ * adds log(w_j / sum_k w_k) = log p_j, the model's probability of the prescribed choice: over a full
+ * enumeration of the choice sequences from one state the weights sum to one.
+ *
+ * Inside an epoch both keep the row's last choice and leave BMPC_ENV_LOGW alone, as mode 1 does. */
+#define BMPC_ENV_LOGW 15
+enum { BMPC_OBS_SAMPLE_TILTED = 2, BMPC_OBS_SCRIPT = 3 };
+typedef struct {
+  double tilt[BMPC_MAX_M];  /* b_j, finite and > 0 for j < m (mode BMPC_OBS_SAMPLE_TILTED)               */
+  const int32_t* script;    /* device table [batch][script_epochs], caller-owned (mode BMPC_OBS_SCRIPT)  */
+  int32_t script_epochs;    /* >= 0; 0: no script                                                        */
+  int32_t epoch0;           /* >= 0: the epoch of the table's column 0                                   */
+} bmpc_obstacle_proposal;
+#ifdef __cplusplus
+static_assert(sizeof(bmpc_obstacle_proposal) == 8 * BMPC_MAX_M + 16 && offsetof(bmpc_obstacle_proposal, tilt) == 0 &&
+                  offsetof(bmpc_obstacle_proposal, script) == 8 * BMPC_MAX_M &&
+                  offsetof(bmpc_obstacle_proposal, script_epochs) == 8 * BMPC_MAX_M + 8 &&
+                  offsetof(bmpc_obstacle_proposal, epoch0) == 8 * BMPC_MAX_M + 12,
+              "bmpc_obstacle_proposal is 48 bytes: tilt 0, script 32, script_epochs 40, epoch0 44");
+#endif
+
+/* Attach (a copy of *q: the plan keeps one on the host and one on the device, which the scene
+ * kernels read through one pointer) or detach (q == NULL) the plan's obstacle proposal.  The script
+ * table itself stays the caller's and must outlive its use.  Re-attaching waits for the plan's
+ * streams before the device copy is overwritten, so a loop already launched keeps what it was
+ * launched with.  While the sampler's mode is BMPC_OBS_SCRIPT every entry that steps a scene --
+ * bmpc_env_step, bmpc_quad_env_step, bmpc_loop_device, bmpc_quad_loop_device -- checks on the host,
+ * before anything is enqueued, that the epochs of its steps lie in [epoch0, epoch0 + script_epochs),
+ * and returns -22 otherwise.  -22 with a message for a tilt entry (j < m) that is not finite and
+ * > 0, script_epochs < 0 or epoch0 < 0, script_epochs > 0 with a null table, detaching (or dropping
+ * the script) while the sampler's mode needs it, and the plans bmpc_set_obstacle_sampling refuses;
+ * bmpc_set_obstacle_sampling in turn refuses modes 2 and 3 without a proposal and mode 3 without
+ * a script. */
+int bmpc_set_obstacle_proposal(bmpc_plan* plan, const bmpc_obstacle_proposal* q);
 
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of

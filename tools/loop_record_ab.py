@@ -53,9 +53,10 @@ class Libraries:
         plan._CTX = self.ctx[name]
 
 
-def run(shape, egos, steps, warmup, seed, record, obstacle=None):
+def run(shape, egos, steps, warmup, seed, record, obstacle=None, proposal=None):
     """One repetition: a fresh plan, `warmup` steps, then `steps` timed ones.  record: None, "core", "full";
-    obstacle: None or the keyword arguments of BatchPlan.set_obstacle_sampling (tools/obstacle_sampling_ab.py)."""
+    obstacle: None or the keyword arguments of BatchPlan.set_obstacle_sampling (tools/obstacle_sampling_ab.py);
+    proposal: None or those of BatchPlan.set_obstacle_proposal, attached first (tools/obstacle_proposal_ab.py)."""
     import torch
     dev = torch.device("cuda", 0)
     f64 = dict(dtype=torch.float64, device=dev)
@@ -81,6 +82,8 @@ def run(shape, egos, steps, warmup, seed, record, obstacle=None):
     st, it = (torch.zeros(egos, dtype=torch.int32, device=dev) for _ in range(2))
     stats = torch.zeros((egos, abi.ENV_NSTAT), **f64)
     tx, tz, tr = (torch.zeros((egos, n), **f64) for _ in range(3))
+    if proposal:
+        pl.set_obstacle_proposal(**proposal)
     if obstacle:
         pl.set_obstacle_sampling(**obstacle)
     rec = None
