@@ -133,6 +133,9 @@ _SIGS = {
     "bmpc_set_loop_record": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_set_obstacle_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_set_obstacle_proposal": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bmpc_population_ancestors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "bmpc_gather_egos": (C.c_int, [C.c_void_p] * 4),
+    "bmpc_resample_device": (C.c_int, [C.c_void_p] * 6),
     "bmpc_qp_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5
                       + [C.c_int, C.c_double] + [C.c_void_p] * 5),
 }

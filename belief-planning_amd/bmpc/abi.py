@@ -191,6 +191,57 @@ def make_obstacle_proposal(tilt=None, script=None, epoch0=0, m=None):
     return P
 
 
+RESAMPLE_SYSTEMATIC = 0        # bmpc_resample_desc.scheme (include/bmpc.h BMPC_RESAMPLE_*)
+RESAMPLE_NINFO = 8             # doubles of the info vector (R_* slots)
+RESAMPLE_MAX_BATCH = 1 << 20
+R_RESAMPLED, R_ESS, R_MAX, R_NEW_LOGW, R_SUM, R_SURVIVORS, R_NONFINITE = range(7)
+
+
+class ResampleDesc(C.Structure):
+    """bmpc_resample_desc: one resampling of a weighted population (bmpc_population_ancestors,
+    bmpc_resample_device; bmpc.resample restates the rule)."""
+    _fields_ = [("scheme", C.c_int32), ("round", C.c_uint32), ("ess_fraction", C.c_double), ("seed", C.c_uint64),
+                ("ego_base", C.c_int64)]
+
+
+def make_resample_desc(round, seed=0, ess_fraction=0.5, ego_base=0, scheme=RESAMPLE_SYSTEMATIC):
+    """Validated bmpc_resample_desc: round in [0, 2^32) addresses the draw (e.g. the step at which the
+    population is resampled), a seed of 64 bits, ess_fraction finite and >= 0 (resample iff
+    ess < ess_fraction * batch: 0 never does, anything above 1 always), ego_base >= 0."""
+    if int(scheme) != RESAMPLE_SYSTEMATIC:
+        raise ValueError("scheme: abi.RESAMPLE_SYSTEMATIC")
+    if int(round) != round or not 0 <= int(round) < 2 ** 32:
+        raise ValueError("round must be an integer in [0, 2^32)")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if not (np.isfinite(ess_fraction) and ess_fraction >= 0):
+        raise ValueError("ess_fraction must be finite and >= 0")
+    if int(ego_base) != ego_base or not 0 <= int(ego_base) < 2 ** 63:
+        raise ValueError("ego_base must be an integer of at least 0")
+    D = ResampleDesc()
+    D.scheme, D.round, D.ess_fraction, D.seed, D.ego_base = int(scheme), int(round), float(ess_fraction), int(seed), \
+        int(ego_base)
+    return D
+
+
+class EgoBuffers(C.Structure):
+    """bmpc_ego_buffers: the loop entries' per-ego device buffers (None skips one)."""
+    _fields_ = [(k, C.c_void_p) for k in ("scene", "upred", "x", "z", "xref", "J", "status", "iters", "stats")]
+
+
+def make_ego_buffers(buffers=None, **named):
+    """bmpc_ego_buffers from a mapping (or keywords) name -> device pointer or torch tensor; the names
+    are EgoBuffers' fields."""
+    E = EgoBuffers()
+    items = dict(buffers or {}, **named)
+    unknown = set(items) - {k for k, _ in EgoBuffers._fields_}
+    if unknown:
+        raise ValueError(f"unknown ego buffers {sorted(unknown)}")
+    for k, v in items.items():
+        setattr(E, k, None if v is None else int(v.data_ptr()) if hasattr(v, "data_ptr") else int(v))
+    return E
+
+
 def _fill(arr, values):
     v = np.asarray(values, dtype=np.float64).ravel()
     for i, x in enumerate(v):

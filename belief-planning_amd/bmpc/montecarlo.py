@@ -85,6 +85,26 @@ def estimate(values, logw, self_normalised=False):
     return estimate_from_terms(reduce_terms(f, lw, shift), self_normalised, shift)
 
 
+def lineage(ancestor_history):
+    """The slots a resampled population's final egos lived in.  ancestor_history: the ancestor arrays
+    [B] of R resamplings in time order (BatchPlan.resample; number r was applied between loop
+    segments r and r + 1).  Returns int64 [B, R + 1]: entry (e, s) is the slot final ego e occupied
+    during segment s -- its last column is e itself, and column s is ancestor_s[column s + 1].  An
+    ego's full trajectory is read out of a LoopRecording (whose rows stay addressed by slot) as the
+    rows of segment s at slot lineage[e, s]."""
+    hist = [np.asarray(a).ravel().astype(np.int64) for a in ancestor_history]
+    if not hist:
+        raise ValueError("at least one ancestor array")
+    B = hist[0].size
+    if any(a.size != B for a in hist) or any(a.min() < 0 or a.max() >= B for a in hist):
+        raise ValueError(f"every ancestor array must hold {B} entries in [0, {B})")
+    out = np.empty((B, len(hist) + 1), np.int64)
+    out[:, -1] = np.arange(B)
+    for s in range(len(hist) - 1, -1, -1):
+        out[:, s] = hist[s][out[:, s + 1]]
+    return out
+
+
 def exact_expectation(values, logp):
     """sum_paths exp(logp) values over a full enumeration (script mode's ENV_LOGW), and the total
     probability sum_paths exp(logp), which is 1 up to rounding when every path is there."""

@@ -343,6 +343,47 @@ class BatchPlan:
               "bmpc_set_obstacle_proposal")
         self.obstacle_proposal, self._script = struct, keep
 
+    # ---- resampling a weighted population ------------------------------------------------------
+    def _ego_buffers(self, buffers):
+        return buffers if isinstance(buffers, abi.EgoBuffers) else abi.make_ego_buffers(buffers)
+
+    def resample(self, buffers, round, seed=0, ess_fraction=0.5, ego_base=0, stream=None):
+        """Resample the plan's weighted population between two loop calls (bmpc_resample_device):
+        ancestors from the scene's abi.ENV_LOGW column by the rule of bmpc.resample (systematic, at the
+        draw bmpc.resample.offset(seed, ego_base, round), iff ess < ess_fraction * batch), then every
+        ego j with ancestor[j] != j becomes a copy of ego ancestor[j] -- its rows of `buffers`, its
+        policies and its warm start -- and every ego's log-weight becomes the log of the mean weight.
+        buffers: a mapping from abi.EgoBuffers' names (scene, upred, x, z, xref, J, status, iters,
+        stats) to the loop's torch tensors or device pointers ("scene" is required), or an
+        abi.EgoBuffers.  Asynchronous on `stream`, like loop_device.  Returns (ancestor [batch] int32,
+        info [abi.RESAMPLE_NINFO] float64) as torch tensors on the plan's device (abi.R_* slots;
+        info[abi.R_RESAMPLED] says whether anything moved).  The recorder is not touched: rows stay
+        addressed by slot, and the ancestors are the genealogy (montecarlo.lineage)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        desc = abi.make_resample_desc(round, seed, ess_fraction, ego_base)
+        bufs = self._ego_buffers(buffers)
+        anc = torch.empty(self.batch, dtype=torch.int32, device=dev)
+        info = torch.empty(abi.RESAMPLE_NINFO, dtype=torch.float64, device=dev)
+        check(lib().bmpc_resample_device(self._h, C.byref(desc), C.byref(bufs), C.c_void_p(anc.data_ptr()),
+                                         C.c_void_p(info.data_ptr()), C.c_void_p(stream) if stream else None),
+              "bmpc_resample_device")
+        return anc, info
+
+    def gather_egos(self, ancestor, buffers=None, stream=None):
+        """Ego j continues as a copy of ego ancestor[j], for every j, as the egos were before the call
+        (bmpc_gather_egos): any map -- a permutation, a broadcast -- of int32 entries clamped to the
+        batch.  ancestor: a torch int32 tensor [batch] on the plan's device, or a device pointer;
+        buffers as in resample (None: only the plan's own state moves).  Asynchronous on `stream`."""
+        ptr = ancestor.data_ptr() if hasattr(ancestor, "data_ptr") else int(ancestor)
+        if hasattr(ancestor, "dtype"):
+            import torch
+            if ancestor.dtype != torch.int32 or ancestor.numel() != self.batch or not ancestor.is_contiguous():
+                raise ValueError(f"ancestor must be a contiguous int32 tensor of {self.batch} entries")
+        bufs = None if buffers is None else self._ego_buffers(buffers)
+        check(lib().bmpc_gather_egos(self._h, C.c_void_p(ptr), None if bufs is None else C.byref(bufs),
+                                     C.c_void_p(stream) if stream else None), "bmpc_gather_egos")
+
     def new_loop_record(self, capacity, t_base=0, predictions=False, device=None):
         """A LoopRecording of `capacity` rows per ego from closed-loop step `t_base` on, in fresh
         zeroed torch tensors on `device` (default: the plan's); predictions adds the optional
@@ -477,6 +518,37 @@ class BatchPlan:
         cnt = C.c_int32()
         check(lib().bmpc_timing(self._h, _p(ms), C.byref(cnt)), "bmpc_timing")
         return dict(tree_ms=float(ms[0]), ipm_ms=float(ms[1]), count=int(cnt.value))
+
+
+def population_ancestors(logw, round, seed=0, ess_fraction=0.5, ego_base=0, stride=1, batch=None, weights=True,
+                         device: int = 0, stream=None):
+    """The resampling rule alone, on the GPU (bmpc_population_ancestors): a pure function of the
+    log-weights that needs no plan.  logw: a float64 torch tensor on the device (entry e at
+    logw.flatten()[e * stride]; batch defaults to numel // stride -- a scene tensor's ENV_LOGW
+    column is ``scene[:, abi.ENV_LOGW:]`` flattened, stride abi.ENV_STRIDE) or any host array, which
+    is uploaded.  Returns torch tensors on the device: (ancestor [batch] int32, k [batch] int64 --
+    the integer weights used, bit patterns of the C side's uint64, or None with weights=False --,
+    info [abi.RESAMPLE_NINFO]).  Asynchronous on `stream` (None: the context's own stream, which is
+    not ordered with torch's: synchronise the device before reading)."""
+    import torch
+    dev = torch.device("cuda", device)
+    if not hasattr(logw, "data_ptr"):
+        logw = torch.tensor(np.ascontiguousarray(np.asarray(logw, np.float64)), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+    if logw.dtype != torch.float64 or not logw.is_contiguous():
+        raise ValueError("logw must be a contiguous float64 tensor")
+    B = (logw.numel() + int(stride) - 1) // int(stride) if batch is None else int(batch)
+    if int(stride) >= 1 and B >= 1 and (B - 1) * int(stride) >= logw.numel():
+        raise ValueError(f"{B} entries at stride {stride} do not fit a tensor of {logw.numel()}")
+    desc = abi.make_resample_desc(round, seed, ess_fraction, ego_base)
+    anc = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+    k = torch.empty(max(B, 1), dtype=torch.int64, device=dev) if weights else None
+    info = torch.empty(abi.RESAMPLE_NINFO, dtype=torch.float64, device=dev)
+    check(lib().bmpc_population_ancestors(context(device), C.byref(desc), B, C.c_void_p(logw.data_ptr()), int(stride),
+                                          C.c_void_p(anc.data_ptr()), C.c_void_p(k.data_ptr()) if weights else None,
+                                          C.c_void_p(info.data_ptr()), C.c_void_p(stream) if stream else None),
+          "bmpc_population_ancestors")
+    return anc, k, info
 
 
 def model_eval(desc: abi.PlanDesc, pol_rows, x, u, z, device: int = 0, lane_ref=None):

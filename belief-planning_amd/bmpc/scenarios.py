@@ -399,6 +399,87 @@ def weighted_quadruped_population(B, steps, seed=0, device=0, record=False, obst
     return _with_logw(_quadruped_loop(pl, scene0, steps, record, device))
 
 
+def _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record, device):
+    """`steps` closed-loop steps from t = 0 of the overtake or quadruped plan `pl` in loop calls of
+    `resample_every` steps with BatchPlan.resample (round = the step t the next call starts at)
+    between them, all on one stream without a host synchronisation; closes the plan.  Returns
+    (stats, scene[, record]) and the list of (ancestor, info) per resampling."""
+    import torch
+    steps, every = int(steps), int(resample_every)
+    if every < 1 or every % int(hold):
+        raise ValueError(f"resample_every must be a positive multiple of hold = {hold}")
+    B, n, d = pl.batch, pl.desc.n, pl.desc.d
+    quad = pl.desc.model == abi.MODEL_QUADRUPED
+    dev = torch.device("cuda", device)
+    f64 = dict(dtype=torch.float64, device=dev)
+    b = dict(scene=torch.tensor(scene0, **f64), upred=torch.zeros((B, pl.U, d), **f64), x=torch.zeros((B, n), **f64),
+             z=torch.zeros((B, n), **f64), xref=torch.zeros((B, n), **f64), J=torch.zeros(B, **f64),
+             status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
+             stats=torch.zeros((B, abi.ENV_NSTAT), **f64))
+    rec = _attach_record(pl, steps, record)
+    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
+    stream = torch.cuda.Stream(dev)
+    env = abi.make_quad_env() if quad else abi.make_env()
+    loop = pl.quad_loop_device if quad else pl.loop_device
+    rounds = []
+    for t in range(0, steps, every):
+        if t > 0:
+            rounds.append(pl.resample(b, t, resample_seed, ess_fraction, ego_base, stream.cuda_stream))
+        loop(env, t, min(every, steps - t), *(b[k].data_ptr() for k in ("scene", "upred", "x", "z", "xref", "J", "status",
+                                                                      "iters", "stats")), stream.cuda_stream)
+    stream.synchronize()
+    out = b["stats"].cpu().numpy(), b["scene"].cpu().numpy()
+    if rec is not None:
+        out += (rec.host(),)
+    pl.close()
+    return out, [(a.cpu().numpy(), i.cpu().numpy()) for a, i in rounds]
+
+
+def resampled_overtake_population(B, steps, resample_every, ess_fraction=0.5, resample_seed=0, tilt=None, seed=0,
+                                  device=0, record=False, obstacle_seed=0, hold=1, ego_base=0, population=None,
+                                  desc=None):
+    """weighted_overtake_population with the population resampled between loop segments: loop calls
+    of `resample_every` steps (a multiple of `hold`) with BatchPlan.resample between them, at round =
+    the step the next call starts at and the draw bmpc.resample.offset(resample_seed, ego_base, round),
+    whenever the effective sample size is below ess_fraction * B.  Egos of large weight are cloned
+    into the slots of egos of negligible weight and all continue with the mean weight, so
+    montecarlo.estimate(f, logw) stays the unbiased plain estimate while the solves go where the
+    probability mass is.  Returns weighted_overtake_population's tuple plus the list of
+    (ancestor [B], info [abi.RESAMPLE_NINFO]) per resampling; with `record` the record's rows stay
+    addressed by slot and montecarlo.lineage(ancestors) tells which slot a final ego lived in.  A
+    sharded run (ego_base = distributed.shard(...)[0]) resamples every shard by itself: a shard's mean
+    weight carries its mass, and montecarlo.reduce_terms over the shards stays the plain estimate."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
+    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
+    pl.set_policies(highway_policy_rows(tgt))
+    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
+    scene0 = np.zeros((B, abi.ENV_STRIDE))
+    scene0[:, abi.ENV_X:abi.ENV_X + 4], scene0[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
+    out, rounds = _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record,
+                                  device)
+    return _with_logw(out) + (rounds,)
+
+
+def resampled_quadruped_population(B, steps, resample_every, ess_fraction=0.5, resample_seed=0, tilt=None, seed=0,
+                                   device=0, record=False, obstacle_seed=0, hold=1, ego_base=0, population=None,
+                                   desc=None):
+    """weighted_quadruped_population with the population resampled between loop segments:
+    resampled_overtake_population's arguments and results (a sharded run, ego_base =
+    distributed.shard(...)[0], resamples every shard by itself)."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
+    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
+    pl.set_policies(quadruped_policy_rows(B))
+    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
+    scene0 = quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows])
+    out, rounds = _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record,
+                                  device)
+    return _with_logw(out) + (rounds,)
+
+
 def enumerated_overtake_population(x0, z0, epochs, hold, device=0, record=False, desc=None):
     """One initial state (x0, z0) against every obstacle choice sequence of `epochs` epochs of `hold`
     steps: m ** epochs egos, ego e following row e of montecarlo.enumerate_scripts(m, epochs)

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bmpc_dev.h"
+#include "bmpc_resample.h"
 
 using namespace bmpc;
 using namespace bmpc::dev;
@@ -123,6 +124,160 @@ __global__ void k_scatter(double* __restrict__ ws, size_t stride, size_t off, in
 __global__ void k_reset(double* ws, size_t stride, size_t off, const uint8_t* mask, int batch) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < batch && (!mask || mask[e])) ws[e * stride + off + MISC_INIT] = 0.0;
+}
+
+// ---- population resampling (bmpc_resample.h holds the per-element rules) ---------------------------
+// One workgroup of kPopThreads threads walks the population in tiles of kPopThreads egos (coalesced
+// loads, a running carry between tiles): at most 2^20 egos, a handful of passes -- a second
+// workgroup would need a device-wide boundary between the passes and buy nothing at these sizes.
+constexpr int kPopThreads = 1024;
+constexpr int kPopWaves = kPopThreads / 64;
+
+// inclusive scan of v over the workgroup; *total = the workgroup's sum.  sh: kPopWaves slots.
+__device__ __forceinline__ uint64_t pop_block_scan(uint64_t v, uint64_t* sh, uint64_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t incl = wave_scan_u64(v);
+  __syncthreads();   // the previous use of sh is over
+  if (lane == 63) sh[wave] = incl;
+  __syncthreads();
+  uint64_t before = 0, all = 0;
+  for (int w = 0; w < kPopWaves; ++w) {
+    const uint64_t s = sh[w];
+    before += w < wave ? s : 0;
+    all += s;
+  }
+  *total = all;
+  return before + incl;
+}
+
+// the workgroup's max of v (NaN-free) in every thread.  sh: kPopThreads doubles.
+__device__ __forceinline__ double pop_block_max(double v, double* sh) {
+  __syncthreads();
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = kPopThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+// the workgroup's sum of a 128-bit integer in every thread.  sh: 2 * kPopThreads uint64.
+__device__ __forceinline__ u128 pop_block_sum128(u128 v, uint64_t* sh) {
+  __syncthreads();
+  sh[2 * threadIdx.x] = (uint64_t)v;
+  sh[2 * threadIdx.x + 1] = (uint64_t)(v >> 64);
+  __syncthreads();
+  for (int s = kPopThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      const u128 a = ((u128)sh[2 * threadIdx.x + 1] << 64) | sh[2 * threadIdx.x];
+      const u128 b = ((u128)sh[2 * (threadIdx.x + s) + 1] << 64) | sh[2 * (threadIdx.x + s)];
+      const u128 c = a + b;
+      sh[2 * threadIdx.x] = (uint64_t)c;
+      sh[2 * threadIdx.x + 1] = (uint64_t)(c >> 64);
+    }
+    __syncthreads();
+  }
+  return ((u128)sh[1] << 64) | sh[0];
+}
+
+// bmpc_population_ancestors: log-weights -> ancestors, the k used and the info vector.  C, Pk: scratch
+// of `batch` uint64 each (the prefix sums of k, then of the packed (dead, surplus) pairs).
+__global__ __launch_bounds__(kPopThreads) void k_pop_ancestors(bmpc_resample_desc D, int batch,
+                                                               const double* __restrict__ logw, int stride,
+                                                               int32_t* __restrict__ anc, uint64_t* __restrict__ weight,
+                                                               double* __restrict__ info, uint64_t* C, uint64_t* Pk) {
+  __shared__ uint64_t sh[2 * kPopThreads];
+  const int tid = threadIdx.x;
+  // pass 1: the maximum, and whether any log-weight refuses the resampling
+  double mx = -INFINITY;
+  uint64_t bad = 0;
+  for (int i = tid; i < batch; i += kPopThreads) {
+    const double lw = logw[(size_t)i * stride];
+    bad += resample_bad_logw(lw) ? 1 : 0;
+    mx = lw > mx && lw < INFINITY ? lw : mx;
+  }
+  const double M = pop_block_max(mx, reinterpret_cast<double*>(sh));
+  const uint64_t nbad = (uint64_t)pop_block_sum128(bad, sh);
+  uint64_t S = 0;
+  double ess = 0.0, lw_new = 0.0;
+  bool resampled = false;
+  if (nbad == 0 && M > -INFINITY) {
+    // pass 2: quantise, scan, sum of squares
+    u128 q = 0;
+    for (int base = 0; base < batch; base += kPopThreads) {
+      const int i = base + tid;
+      const uint64_t k = i < batch ? resample_quantise(logw[(size_t)i * stride], M) : 0;
+      if (i < batch && weight) weight[i] = k;
+      q += (u128)k * k;
+      uint64_t total;
+      const uint64_t incl = pop_block_scan(k, sh, &total);
+      if (i < batch) C[i] = S + incl;
+      S += total;
+    }
+    const u128 Q = pop_block_sum128(q, sh);
+    ess = resample_ess(S, Q);
+    lw_new = resample_new_logw(M, S, batch);
+    resampled = ess < D.ess_fraction * (double)batch;
+  } else if (weight) {
+    for (int i = tid; i < batch; i += kPopThreads) weight[i] = 0;
+  }
+  uint64_t dead = 0;
+  if (!resampled) {
+    for (int i = tid; i < batch; i += kPopThreads) anc[i] = i;
+  } else {
+    // pass 3: children per slot from the prefix sums, the packed (dead, surplus) scan
+    __syncthreads();   // C is complete
+    const u128 U0 = resample_offset(resample_u53(D.seed, (uint64_t)D.ego_base, D.round), S);
+    uint64_t carry = 0;
+    for (int base = 0; base < batch; base += kPopThreads) {
+      const int i = base + tid;
+      uint64_t v = 0;
+      if (i < batch) {
+        const int hi = resample_children_below(C[i], S, U0, batch);
+        const int lo = i ? resample_children_below(C[i - 1], S, U0, batch) : 0;
+        v = resample_pack(hi - lo);
+      }
+      uint64_t total;
+      const uint64_t incl = pop_block_scan(v, sh, &total);
+      if (i < batch) Pk[i] = carry + incl;
+      carry += total;
+    }
+    dead = carry >> 32;
+    // pass 4: the arrangement
+    __syncthreads();   // Pk is complete
+    for (int i = tid; i < batch; i += kPopThreads) anc[i] = resample_arrange(Pk, batch, i);
+  }
+  if (tid == 0) {
+    info[0] = resampled ? 1.0 : 0.0;
+    info[1] = ess;
+    info[2] = M;
+    info[3] = lw_new;
+    info[4] = (double)S;
+    info[5] = (double)(batch - (int)dead);
+    info[6] = (double)nbad;
+    info[7] = 0.0;
+  }
+}
+
+// bmpc_gather_egos, pass 1 and pass 2: one workgroup per ego (bmpc_resample.h, gather_stage_ego /
+// gather_commit_ego).  flag: null, or the info vector of the resampling that made `anc` -- nothing
+// moves when its "resampled" entry is 0.
+__global__ __launch_bounds__(256) void k_ego_stage(GatherList G, const int32_t* __restrict__ anc,
+                                                   uint32_t* __restrict__ stage, const double* flag) {
+  if (flag && flag[0] == 0.0) return;
+  gather_stage_ego(G, anc, stage, blockIdx.x, threadIdx.x, blockDim.x);
+}
+__global__ __launch_bounds__(256) void k_ego_commit(GatherList G, const int32_t* __restrict__ anc,
+                                                    const uint32_t* __restrict__ stage, const double* flag) {
+  if (flag && flag[0] == 0.0) return;
+  gather_commit_ego(G, anc, stage, blockIdx.x, threadIdx.x, blockDim.x);
+}
+
+// bmpc_resample_device's last stage: the log of the mean weight into every ego's BMPC_ENV_LOGW
+__global__ void k_pop_set_logw(double* scene, int batch, const double* info) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < batch && info[0] != 0.0) scene[(size_t)e * ENV_STRIDE + BMPC_ENV_LOGW] = info[3];
 }
 
 template <class M>
@@ -337,7 +492,12 @@ struct bmpc_ctx {
   // the QP cache above; ctypes releases the GIL during a call, so calls from several host
   // threads on one context are serialised here
   std::mutex q_mu;
+  // bmpc_population_ancestors: its scratch (the two scans) and the event that orders one call's use
+  // of it before the next call's, whichever streams they run on
+  GrowBuf r_scratch;
+  hipEvent_t r_done = nullptr;
   ~bmpc_ctx() {
+    if (r_done) hipEventDestroy(r_done);
     if (qstream) hipStreamDestroy(qstream);
   }
 };
@@ -385,6 +545,7 @@ struct bmpc_plan {
   bmpc_obstacle_proposal prop = {};
   bmpc_obstacle_proposal* d_prop = nullptr;
   bool has_prop = false;
+  uint64_t* d_rs = nullptr;   // bmpc_resample_device's scans (2 * batch uint64, allocated at the first call)
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
 
@@ -518,6 +679,7 @@ int bmpc_plan_destroy(bmpc_plan* pl) {
   hipFree(pl->d_lref);
   hipFree(pl->d_mref);
   hipFree(pl->d_prop);
+  hipFree(pl->d_rs);
   hipFree(pl->d_blk_lay);
   for (auto& e : pl->ev)
     if (e) hipEventDestroy(e);
@@ -1134,6 +1296,109 @@ int bmpc_set_obstacle_proposal(bmpc_plan* pl, const bmpc_obstacle_proposal* q) {
   HIPCHECK(hipMemcpy(pl->d_prop, &h, sizeof(h), hipMemcpyHostToDevice));
   pl->prop = h;
   pl->has_prop = true;
+  return 0;
+}
+
+// "" for a resampling description and batch the ancestor rule takes
+static std::string check_resample(const bmpc_resample_desc* d, int batch) {
+  if (batch < 1 || batch > BMPC_RESAMPLE_MAX_BATCH) return "batch must lie in 1 .. BMPC_RESAMPLE_MAX_BATCH (2^20)";
+  if (d->scheme != BMPC_RESAMPLE_SYSTEMATIC) return "unknown scheme (BMPC_RESAMPLE_SYSTEMATIC)";
+  if (!(std::isfinite(d->ess_fraction) && d->ess_fraction >= 0.0)) return "ess_fraction must be finite and >= 0";
+  if (d->ego_base < 0) return "ego_base must not be negative";
+  return "";
+}
+
+// the ancestor kernel on s (scratch: 2 * batch uint64)
+static int launch_ancestors(const bmpc_resample_desc& d, int batch, const double* d_logw, int stride,
+                            int32_t* d_anc, uint64_t* d_weight, double* d_info, uint64_t* scratch, hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_ancestors, dim3(1), dim3(kPopThreads), 0, s, d, batch, d_logw, stride, d_anc, d_weight,
+                     d_info, scratch, scratch + batch);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+int bmpc_population_ancestors(bmpc_ctx* ctx, const bmpc_resample_desc* desc, int batch, const double* d_logw,
+                              int stride, int32_t* d_ancestor, uint64_t* d_weight, double* d_info, void* stream) {
+  if (!ctx || !desc || !d_logw || !d_ancestor || !d_info)
+    return fail(-22, "bmpc_population_ancestors: null argument (ctx, desc, d_logw, d_ancestor and d_info are required)");
+  if (stride < 1) return fail(-22, "bmpc_population_ancestors: stride must be at least 1");
+  if (const std::string e = check_resample(desc, batch); !e.empty()) return fail(-22, "bmpc_population_ancestors: " + e);
+  std::lock_guard<std::mutex> lock(ctx->q_mu);
+  HIPCHECK(hipSetDevice(ctx->device));
+  if (!ctx->qstream) HIPCHECK(hipStreamCreateWithFlags(&ctx->qstream, hipStreamNonBlocking));
+  if (!ctx->r_done) HIPCHECK(hipEventCreateWithFlags(&ctx->r_done, hipEventDisableTiming));
+  hipStream_t s = stream ? (hipStream_t)stream : ctx->qstream;
+  // (a reallocation frees the old scratch, which waits for the device; otherwise the last call's
+  // kernel, on whichever stream, finishes with the scratch before this one starts)
+  HIPCHECK(ctx->r_scratch.reserve(2 * sizeof(uint64_t) * (size_t)batch));
+  HIPCHECK(hipStreamWaitEvent(s, ctx->r_done, 0));
+  if (const int rc = launch_ancestors(*desc, batch, d_logw, stride, d_ancestor, d_weight, d_info,
+                                      ctx->r_scratch.as<uint64_t>(), s))
+    return rc;
+  HIPCHECK(hipEventRecord(ctx->r_done, s));
+  return 0;
+}
+
+// the gather of a plan's egos through `anc` on s, under `flag` (null: unconditionally)
+static int launch_gather(bmpc_plan* pl, const int32_t* d_anc, const bmpc_ego_buffers* b, const double* flag,
+                         hipStream_t s) {
+  const Plan& P = pl->hp.plan;
+  const Layout& L = pl->hp.lay;
+  GatherList G = {};
+  G.batch = pl->batch;
+  bool ok = true;
+  const size_t n = P.n, ud = (size_t)P.U * P.d;
+  if (b) {   // (words are 4 bytes: a double is 2)
+    ok = ok && gather_add(G, b->scene, 2 * ENV_STRIDE, 0, 2 * ENV_STRIDE) && gather_add(G, b->upred, 2 * ud, 0, 2 * ud) &&
+         gather_add(G, b->x, 2 * n, 0, 2 * n) && gather_add(G, b->z, 2 * n, 0, 2 * n) &&
+         gather_add(G, b->xref, 2 * n, 0, 2 * n) && gather_add(G, b->J, 2, 0, 2) && gather_add(G, b->status, 1, 0, 1) &&
+         gather_add(G, b->iters, 1, 0, 1) && gather_add(G, b->stats, 2 * ENVS_STRIDE, 0, 2 * ENVS_STRIDE);
+  }
+  static_assert(sizeof(bmpc_policy) % 4 == 0, "policy rows are copied as 4-byte words");
+  const size_t polw = sizeof(bmpc_policy) / 4 * P.m;
+  ok = ok && gather_add(G, pl->d_pol, polw, 0, polw);
+  EgoSpan spans[EGO_MAX_SPANS];
+  const int nsp = ego_state_spans(P, L, spans);
+  for (int k = 0; k < nsp; ++k) ok = ok && gather_add(G, pl->d_ws, 2 * L.stride, 2 * spans[k].off, 2 * spans[k].len);
+  if (!ok) return fail(-5, "bmpc_gather_egos: segment list overflow");
+  const size_t need = ((size_t)pl->batch * G.row_words + 1) / 2;   // doubles of the plan's scratch
+  if (need > pl->scratch_len) {
+    hipFree(pl->d_scratch);   // (waits for the device: nothing in flight reads the old scratch)
+    pl->d_scratch = nullptr;
+    pl->scratch_len = 0;
+    HIPCHECK(hipMalloc(&pl->d_scratch, need * sizeof(double)));
+    pl->scratch_len = need;
+  }
+  uint32_t* stage = reinterpret_cast<uint32_t*>(pl->d_scratch);
+  hipLaunchKernelGGL(k_ego_stage, dim3(pl->batch), dim3(256), 0, s, G, d_anc, stage, flag);
+  HIPCHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_ego_commit, dim3(pl->batch), dim3(256), 0, s, G, d_anc, stage, flag);
+  HIPCHECK(hipGetLastError());
+  pl->pol_on_device = true;   // policy rows moved on the device: h_pol is stale
+  return 0;
+}
+
+int bmpc_gather_egos(bmpc_plan* pl, const int32_t* d_ancestor, const bmpc_ego_buffers* bufs, void* stream) {
+  if (!pl || !d_ancestor) return fail(-22, "bmpc_gather_egos: null argument (plan and d_ancestor are required)");
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  return launch_gather(pl, d_ancestor, bufs, nullptr, plan_stream(pl, stream));
+}
+
+int bmpc_resample_device(bmpc_plan* pl, const bmpc_resample_desc* desc, const bmpc_ego_buffers* bufs,
+                         int32_t* d_ancestor, double* d_info, void* stream) {
+  if (!pl || !desc || !bufs || !bufs->scene || !d_ancestor || !d_info)
+    return fail(-22, "bmpc_resample_device: null argument (plan, desc, bufs->scene, d_ancestor and d_info are required)");
+  if (const std::string e = check_obstacle_chooses(pl->hp.plan); !e.empty()) return fail(-22, "bmpc_resample_device: " + e);
+  if (const std::string e = check_resample(desc, pl->batch); !e.empty()) return fail(-22, "bmpc_resample_device: " + e);
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  if (!pl->d_rs) HIPCHECK(hipMalloc(&pl->d_rs, 2 * sizeof(uint64_t) * (size_t)pl->batch));
+  hipStream_t s = plan_stream(pl, stream);
+  if (const int rc = launch_ancestors(*desc, pl->batch, bufs->scene + BMPC_ENV_LOGW, ENV_STRIDE, d_ancestor, nullptr,
+                                      d_info, pl->d_rs, s))
+    return rc;
+  if (const int rc = launch_gather(pl, d_ancestor, bufs, d_info, s)) return rc;
+  hipLaunchKernelGGL(k_pop_set_logw, dim3((pl->batch + 255) / 256), dim3(256), 0, s, bufs->scene, pl->batch, d_info);
+  HIPCHECK(hipGetLastError());
   return 0;
 }
 

@@ -75,6 +75,18 @@ __device__ __forceinline__ double group_reduce(double v, int g) {
   if (g > 1) v = xor_level<1, OP, DPP>(v);
   return v;
 }
+// Inclusive prefix sum of an unsigned 64-bit integer over the wave's 64 lanes (every lane active).
+// Integer sums are associative, so the scan's shape cannot change a bit of the result (the
+// population resampling's scans, bmpc_resample.h).
+__device__ __forceinline__ unsigned long long wave_scan_u64(unsigned long long v) {
+  const int lane = __lane_id();
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  return v;
+}
 }  // namespace dev
 }  // namespace bmpc
 #endif

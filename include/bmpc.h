@@ -36,6 +36,8 @@
  *                         branch_eval's distribution instead of the reference's argmax rules)
  *   bmpc_set_obstacle_proposal   (an extension: the draw tilted per policy, or a prescribed choice
  *                         per ego and epoch, with a running log-weight in the scene row)
+ *   bmpc_population_ancestors / bmpc_gather_egos / bmpc_resample_device   (an extension: resampling a
+ *                         weighted population between loop segments, on the device)
  *
  * Conventions: all host buffers are caller-owned, C-contiguous, ego-major, float64
  * (int32 for status/iteration counts).  Return codes are 0 on success and a negative
@@ -559,6 +561,89 @@ static_assert(sizeof(bmpc_obstacle_proposal) == 8 * BMPC_MAX_M + 16 && offsetof(
  * bmpc_set_obstacle_sampling in turn refuses modes 2 and 3 without a proposal and mode 3 without
  * a script. */
 int bmpc_set_obstacle_proposal(bmpc_plan* plan, const bmpc_obstacle_proposal* q);
+
+/* Resampling a weighted population between loop segments (sequential Monte Carlo / particle
+ * splitting): egos of large weight are cloned into the slots of egos of negligible weight and every
+ * ego continues with the population's mean weight, so that montecarlo.estimate's plain estimate stays
+ * unbiased while the solves go where the probability mass is.  An extension: the reference has no
+ * populations.
+ *
+ * The ancestor rule is exact integer arithmetic (csrc/bmpc_resample.h; bmpc/resample.py restates it):
+ *   M = max logw (M = -inf: nothing is resampled);  k_i = floor(exp(logw_i - M) 2^40) as uint64;
+ *   C the inclusive prefix sums of k, S = C_{B-1}, Q = sum k_i^2 exactly in 128 bits;
+ *   ess = (double)S (double)S / (double)Q, conversions rounded to nearest; resample iff
+ *   ess < ess_fraction * batch in double (any ess_fraction > 1 always resamples);
+ *   one draw per resampling: Philox4x32-10 (csrc/bmpc_rng.h) at counter {lo32(ego_base),
+ *   hi32(ego_base), round, purpose 1}, key = seed; u53 its 53-bit integer ((o0 >> 5) 2^26 + (o1 >> 6)),
+ *   U0 = (u53 S) >> 53;
+ *   systematic resampling: child j's raw ancestor is the smallest i with C_i B > U0 + j S; n_i children
+ *   have raw ancestor i;
+ *   arrangement: a slot with n_i >= 1 keeps ancestor[i] = i; the dead slots (n_i = 0), in increasing
+ *   order, receive the surplus list (each i repeated n_i - 1 times, in increasing i) -- sources are never
+ *   destinations, most egos do not move and a surviving slot's recorder rows stay one trajectory;
+ *   when resampled, every ego's new log-weight is M + log S - log batch - 40 log 2 (the log of the mean
+ *   weight).  A NaN or +inf log-weight refuses the resampling.  When nothing is resampled the ancestors
+ *   are the identity and no byte of any ego changes. */
+enum { BMPC_RESAMPLE_SYSTEMATIC = 0 };
+typedef struct {
+  int32_t  scheme;        /* BMPC_RESAMPLE_SYSTEMATIC (other values reserved: -22)              */
+  uint32_t round;         /* addresses the draw: e.g. the step t at which the population is resampled */
+  double   ess_fraction;  /* resample iff ess < ess_fraction * batch; finite and >= 0              */
+  uint64_t seed;
+  int64_t  ego_base;      /* >= 0, as in bmpc_obstacle_sampling                                   */
+} bmpc_resample_desc;
+#ifdef __cplusplus
+static_assert(sizeof(bmpc_resample_desc) == 32 && offsetof(bmpc_resample_desc, scheme) == 0 &&
+                  offsetof(bmpc_resample_desc, round) == 4 && offsetof(bmpc_resample_desc, ess_fraction) == 8 &&
+                  offsetof(bmpc_resample_desc, seed) == 16 && offsetof(bmpc_resample_desc, ego_base) == 24,
+              "bmpc_resample_desc is 32 bytes: scheme 0, round 4, ess_fraction 8, seed 16, ego_base 24");
+#endif
+
+/* info [BMPC_RESAMPLE_NINFO] doubles: {resampled (0 / 1), ess, M, the new log-weight (log of the mean
+ * weight), (double)S, survivors (slots with n_i >= 1; batch when not resampled), NaN / +inf log-weights
+ * seen, 0}.  With a NaN / +inf log-weight or M = -inf nothing is quantised: ess, the new log-weight and
+ * S are 0 and the weights written are 0. */
+#define BMPC_RESAMPLE_NINFO 8
+#define BMPC_RESAMPLE_MAX_BATCH (1 << 20)
+
+/* The ancestors of a population of `batch` egos from their log-weights d_logw[e * stride] (device
+ * pointers; stride in doubles): d_ancestor [batch] int32, d_weight [batch] uint64 the k_i used (NULL
+ * skips), d_info as above.  A pure function of its inputs that needs no plan.  Enqueued on `stream`
+ * (NULL: a stream of the context's), no host synchronisation; its scratch is kept with the context
+ * and calls on one context are ordered with each other on the device.  -22 with a message for
+ * batch < 1 or > BMPC_RESAMPLE_MAX_BATCH, stride < 1, an unknown scheme, a negative or non-finite
+ * ess_fraction, ego_base < 0 and null required pointers. */
+int bmpc_population_ancestors(bmpc_ctx* ctx, const bmpc_resample_desc* desc, int batch, const double* d_logw,
+                              int stride, int32_t* d_ancestor, uint64_t* d_weight, double* d_info, void* stream);
+
+/* The loop entries' per-ego device buffers with their shapes: scene [batch][BMPC_ENV_STRIDE], upred
+ * [batch][U][d], x / z / xref [batch][n], J / status / iters [batch], stats [batch][BMPC_ENV_NSTAT].
+ * NULL skips a buffer. */
+typedef struct {
+  double *scene, *upred, *x, *z, *xref, *J;
+  int32_t *status, *iters;
+  double* stats;
+} bmpc_ego_buffers;
+
+/* For every j with a[j] != j, ego j becomes a copy of ego a[j] as it was before the call -- for any
+ * map a (a permutation and a broadcast both work: the copies are staged through the plan's scratch);
+ * entries of a are clamped to [0, batch).  What moves: the ego's rows of the given buffers (NULL
+ * bufs: none), its policy row, and the spans of its workspace slab that a later solve or scene step
+ * reads before writing them (csrc/bmpc_resample.h, ego_state_spans: the warm start uLin, the previous
+ * branch probabilities, Jcons / OldInput / the other misc slots, the last predictions and solution,
+ * robustMPC's xLin, the transform slots of transform and merge plans).  Every plan kind; enqueued on
+ * `stream` (NULL: the plan's), no host synchronisation.  The recorder is not touched: rows stay
+ * addressed by slot, and a is the genealogy. */
+int bmpc_gather_egos(bmpc_plan* plan, const int32_t* d_ancestor, const bmpc_ego_buffers* bufs, void* stream);
+
+/* bmpc_population_ancestors from the scene's slot BMPC_ENV_LOGW, then bmpc_gather_egos, then the new
+ * log-weight into slot BMPC_ENV_LOGW of every ego -- all under the device-side "resampled" decision
+ * (the gather kernels read info[0] and do nothing when it is 0), no host synchronisation between the
+ * stages.  bufs->scene, d_ancestor [batch] and d_info [BMPC_RESAMPLE_NINFO] are required.  The plans
+ * bmpc_set_obstacle_sampling accepts; -22 otherwise with the same messages, and for what
+ * bmpc_population_ancestors refuses. */
+int bmpc_resample_device(bmpc_plan* plan, const bmpc_resample_desc* desc, const bmpc_ego_buffers* bufs,
+                         int32_t* d_ancestor, double* d_info, void* stream);
 
 /* HMM belief-augmented linearisation, batched over B points: replaces
  * HMM_backup_dyn.PredictiveModel.regressionAndLinearization (HMM_backup_dyn.py:216-237) of
