@@ -191,6 +191,40 @@ def make_obstacle_proposal(tilt=None, script=None, epoch0=0, m=None):
     return P
 
 
+DISTURB_NONE, DISTURB_IH4 = 0, 1   # bmpc_disturbance.law (include/bmpc.h BMPC_DISTURB_*)
+
+
+class Disturbance(C.Structure):
+    """bmpc_disturbance: the actuation disturbance of the closed loops' Euler steps
+    (bmpc_set_disturbance; the draws are bmpc.rng.disturbance's).  88 bytes."""
+    _fields_ = [("law", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("ego_base", C.c_int64),
+                ("sigma_ego", C.c_double * MAX_D), ("sigma_obs", C.c_double * MAX_D)]
+
+
+def make_disturbance(sigma_ego=None, sigma_obs=None, seed=0, ego_base=0, law=DISTURB_IH4, d=None):
+    """Validated bmpc_disturbance.  sigma_ego / sigma_obs: the standard deviation per input component
+    of the ego / the obstacle (None: zeros; finite and >= 0, at most MAX_D entries -- d when the
+    plan's input dimension is given), a seed of 64 bits, ego_base >= 0 the global index of the plan's
+    ego 0, law abi.DISTURB_IH4 or abi.DISTURB_NONE."""
+    if int(law) not in (DISTURB_NONE, DISTURB_IH4):
+        raise ValueError("law: abi.DISTURB_NONE or abi.DISTURB_IH4")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if int(ego_base) != ego_base or not 0 <= int(ego_base) < 2 ** 63:
+        raise ValueError("ego_base must be an integer of at least 0")
+    D = Disturbance()
+    D.law, D.seed, D.ego_base = int(law), int(seed), int(ego_base)
+    lim = MAX_D if d is None else int(d)
+    for name, sig in (("sigma_ego", sigma_ego), ("sigma_obs", sigma_obs)):
+        s = np.zeros(0) if sig is None else np.atleast_1d(np.asarray(sig, dtype=np.float64))
+        if s.ndim != 1 or s.size > lim:
+            raise ValueError(f"{name} must hold at most {lim} entries (one per input component), got shape {s.shape}")
+        if not (np.all(np.isfinite(s)) and np.all(s >= 0)):
+            raise ValueError(f"every {name} entry must be finite and >= 0")
+        _fill(getattr(D, name), s)
+    return D
+
+
 RESAMPLE_SYSTEMATIC = 0        # bmpc_resample_desc.scheme (include/bmpc.h BMPC_RESAMPLE_*)
 RESAMPLE_NINFO = 8             # doubles of the info vector (R_* slots)
 RESAMPLE_MAX_BATCH = 1 << 20

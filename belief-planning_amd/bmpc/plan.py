@@ -343,6 +343,27 @@ class BatchPlan:
               "bmpc_set_obstacle_proposal")
         self.obstacle_proposal, self._script = struct, keep
 
+    # ---- the scenes' actuation disturbance ----------------------------------------------------
+    def set_disturbance(self, sigma_ego=None, sigma_obs=None, seed=0, ego_base=0):
+        """Process noise in the plan's closed loops (bmpc_set_disturbance): in the Euler step that
+        follows closed-loop step t the ego of row e moves with
+        ``uPred[0] + sigma_ego * bmpc.rng.disturbance(seed, ego_base + e, t, "ego", d)`` and the
+        obstacle with its chosen input ``+ sigma_obs * bmpc.rng.disturbance(seed, ego_base + e, t,
+        "obstacle", d)`` -- a unit-variance, bounded, near-Gaussian variate per component, the product
+        rounded before it is added.  sigma_ego / sigma_obs: up to d standard deviations >= 0 (None:
+        zeros; a zero component makes no draw).  The scene row's obstacle-input slot and the
+        recorder's u column keep the nominal inputs; nothing is clipped.  All three scenes, both
+        launch paths and the single-step entries obey it; a shard passes ego_base=lo.
+        sigma_ego=None, sigma_obs=None detaches.  Also takes an abi.Disturbance as `sigma_ego`."""
+        if isinstance(sigma_ego, abi.Disturbance):
+            struct = sigma_ego
+        elif sigma_ego is None and sigma_obs is None:
+            struct = None
+        else:
+            struct = abi.make_disturbance(sigma_ego, sigma_obs, seed, ego_base, d=int(self.desc.d))
+        check(lib().bmpc_set_disturbance(self._h, None if struct is None else C.byref(struct)), "bmpc_set_disturbance")
+        self.disturbance = struct
+
     # ---- resampling a weighted population ------------------------------------------------------
     def _ego_buffers(self, buffers):
         return buffers if isinstance(buffers, abi.EgoBuffers) else abi.make_ego_buffers(buffers)

@@ -3,14 +3,18 @@ draw, as ``csrc/bmpc_rng.h`` computes them on the device (``BatchPlan.set_obstac
 
 A draw is addressed by (seed, global ego, epoch), never consumed: anyone can reproduce or audit the
 choice an obstacle made at closed-loop step t from ``obstacle_uniform(seed, ego_base + e, t // hold)``
-and the model's branch probabilities at that step's state (``inverse_cdf``), without a GPU."""
+and the model's branch probabilities at that step's state (``inverse_cdf``), without a GPU.  The
+actuation disturbance (``BatchPlan.set_disturbance``) is addressed the same way: the inputs applied
+after step t are ``nominal + sigma * disturbance(seed, ego_base + e, t, vehicle, d)``."""
 from __future__ import annotations
 
 import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
-PURPOSE_OBSTACLE_POLICY = 0      # counter word 3; other values are reserved
+PURPOSE_OBSTACLE_POLICY = 0      # counter word 3; 1 is bmpc.resample's, 2-7 are reserved
+DISTURBANCE_PURPOSE = {"obstacle": 8, "ego": 12}   # ... + c for component c of the vehicle's input
+DISTURBANCE_SCALE = float.fromhex("0x1.bb67ae8584caap-32")   # sqrt(3) / 2^32
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
 
@@ -56,6 +60,35 @@ def obstacle_uniform(seed, ego, epoch):
     key = np.stack([s & _MASK, s >> _S32], axis=-1)
     o = philox4x32(counter, key)
     return uniform53(o[..., 0], o[..., 1])
+
+
+def ih4(o):
+    """The disturbance's variate from four output words o [..., 4]: the centred integer sum
+    s = o0 + o1 + o2 + o3 - 2 (2^32 - 1), exact, times sqrt(3) / 2^32 -- one rounding, the double
+    ``rng_ih4`` of ``csrc/bmpc_rng.h`` gives.  Irwin-Hall with four terms: mean 0, variance
+    1 - 2^-64, kurtosis 2.7, |xi| <= 2 sqrt(3)."""
+    s = np.asarray(o, dtype=np.uint32).astype(np.int64).sum(axis=-1) - 2 * (2 ** 32 - 1)
+    return s.astype(np.float64) * DISTURBANCE_SCALE
+
+
+def disturbance(seed, ego, step, vehicle, d):
+    """xi [..., d] of the actuation disturbance (``BatchPlan.set_disturbance``): seed its 64-bit
+    seed, ego the GLOBAL ego index (the plan's ego_base + its row), step the closed-loop step t
+    whose input is disturbed, vehicle "obstacle" or "ego", d the input dimension (<= 4).  The input
+    a vehicle applies at step t is ``nominal + sigma * disturbance(...)``, the product rounded before
+    it is added -- what NumPy computes.  Vectorised like ``obstacle_uniform``."""
+    if vehicle not in DISTURBANCE_PURPOSE:
+        raise ValueError(f"vehicle {vehicle!r}: one of {sorted(DISTURBANCE_PURPOSE)}")
+    if int(d) != d or not 1 <= int(d) <= 4:
+        raise ValueError("d must be an integer in 1..4")
+    s, g, t = np.broadcast_arrays(_u64(seed, "seed"), _u64(ego, "ego"), _u64(step, "step"))
+    if t.size and t.max() >= 2 ** 32:
+        raise ValueError("step must fit 32 bits")
+    s, g, t = (np.broadcast_to(a[..., None], a.shape + (int(d),)) for a in (s, g, t))
+    purpose = np.broadcast_to(np.arange(int(d), dtype=np.uint64) + np.uint64(DISTURBANCE_PURPOSE[vehicle]), g.shape)
+    counter = np.stack([g & _MASK, g >> _S32, t, purpose], axis=-1)
+    key = np.stack([s & _MASK, s >> _S32], axis=-1)
+    return ih4(philox4x32(counter, key))
 
 
 def inverse_cdf(p, u):

@@ -212,12 +212,19 @@ def merge_population(B, steps, seed=0, device=0, record=False):
     distributed.episode_stats takes; a step's solve is booked by the next step, so they cover
     steps - 1 solves) and the final scene [B, ENV_STRIDE]; with `record` (overtake_population's)
     also the per-step record on the host."""
-    import torch
     from . import plan
     x, z = seeded_merge_batch(B, seed)
     pl = plan.BatchPlan(merge_desc(), B, device)
     pl.set_policies(merge_policy_rows(B))
     pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
+    return _merge_loop(pl, x, z, steps, record, device)
+
+
+def _merge_loop(pl, x, z, steps, record, device):
+    """`steps` closed-loop steps from t = 0 of the merge plan `pl` (policies and scene set) from the
+    states x, z [B, 4]: the population entries' results; closes the plan."""
+    import torch
+    B = pl.batch
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
     scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
@@ -529,3 +536,65 @@ def quadruped_xref(x, x_des=(5.0, -3.0, 0.0)):
     xr[:, 0:2] += dx
     xr[:, 2] = psi
     return xr
+
+
+def _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base):
+    """The actuation disturbance of a disturbed_*_population call (BatchPlan.set_disturbance); both
+    sigmas None leaves the plan undisturbed."""
+    if sigma_ego is None and sigma_obs is None:
+        return None
+    pl.set_disturbance(sigma_ego, sigma_obs, seed=disturbance_seed, ego_base=ego_base)
+    return pl.disturbance
+
+
+def disturbed_overtake_population(B, steps, sigma_ego=None, sigma_obs=None, disturbance_seed=0, seed=0, device=0,
+                                  record=False, obstacle=None, obstacle_seed=0, hold=1, ego_base=0, population=None,
+                                  desc=None):
+    """sampled_overtake_population under process noise: in every Euler step the ego applies
+    uPred[0] + sigma_ego * xi and the obstacle its chosen input + sigma_obs * xi, xi =
+    bmpc.rng.disturbance(disturbance_seed, global ego, t, vehicle, 2) a unit-variance bounded variate per
+    component (BatchPlan.set_disturbance).  sigma_ego / sigma_obs: standard deviations of
+    (acceleration, yaw rate), None: zeros.  obstacle=None keeps the reference's deterministic choice,
+    "model" also samples it (obstacle_seed, hold).  The sharding rule is sampled_overtake_population's
+    (ego_base = distributed.shard(...)[0]): each ego has the trajectory it has in the unsharded run.
+    The record's u and the scene's obstacle input are the nominal inputs; the applied ones are
+    nominal + sigma * bmpc.rng.disturbance(...)."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
+    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
+    pl.set_policies(highway_policy_rows(tgt))
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    return _overtake_loop(pl, x, z, steps, record, device)
+
+
+def disturbed_merge_population(B, steps, sigma_ego=None, sigma_obs=None, disturbance_seed=0, seed=0, device=0,
+                               record=False, ego_base=0, population=None):
+    """merge_population under process noise (disturbed_overtake_population's disturbance arguments):
+    the merge scene's first source of randomness beyond its initial states.  The B egos are rows
+    ego_base .. ego_base + B - 1 of seeded_merge_batch(population, seed) and draw as those global
+    egos."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z = (a[rows] for a in seeded_merge_batch(total, seed))
+    pl = plan.BatchPlan(merge_desc(), B, device)
+    pl.set_policies(merge_policy_rows(B))
+    pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    return _merge_loop(pl, x, z, steps, record, device)
+
+
+def disturbed_quadruped_population(B, steps, sigma_ego=None, sigma_obs=None, disturbance_seed=0, seed=0, device=0,
+                                   record=False, obstacle=None, obstacle_seed=0, hold=1, ego_base=0, population=None,
+                                   desc=None):
+    """sampled_quadruped_population under process noise: disturbed_overtake_population's arguments,
+    the sigmas those of (vx, vy, yaw rate)."""
+    from . import plan
+    total, rows = _shard_rows(B, ego_base, population)
+    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
+    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
+    pl.set_policies(quadruped_policy_rows(B))
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    return _quadruped_loop(pl, quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), steps, record, device)

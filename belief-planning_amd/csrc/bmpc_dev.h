@@ -407,26 +407,28 @@ __device__ __attribute__((noinline)) IpmResult loop_ipm(const X ex, const Plan& 
 // (smp: the plan's obstacle sampler, bmpc_set_obstacle_sampling, by reference out of the kernel
 // argument like env -- two argument registers; the sampled rule lives in here, on lane 0, under a
 // branch on its mode, so the solve's register budget never sees it.  e: the wave's ego.  prop: the
-// plan's device copy of its obstacle proposal, bmpc_set_obstacle_proposal, or null -- one pointer,
-// read by the weighted modes only.)
+// plan's device block of scene options (bmpc_env.h SceneOptions: its obstacle proposal,
+// bmpc_set_obstacle_proposal, then its disturbance, bmpc_set_disturbance) or null -- one pointer; the
+// proposal is read by the weighted modes only, the disturbance's law once per step.)
 __device__ __attribute__((noinline)) void loop_env_step(const bmpc_env_desc& env, double dt, int N, int m, int t,
                                                         double* st, bmpc_policy* pol, const double* up, double* x,
                                                         double* z, double* xr, double Jv, int status, int iters,
                                                         double* stats, const bmpc_obstacle_sampling& smp,
-                                                        const double* mc, int e,
-                                                        const bmpc_obstacle_proposal* prop) {
+                                                        const double* mc, int e, const SceneOptions* opt) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, true, stats);
-  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, prop);
+  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, scene_prop(opt), scene_dist(opt));
 }
 
 // One merge-scene step of one ego into its slab (k_env_merge and the merge k_loop): the scene
 // function writes S and bx straight into the ego's transform slots and marks them set (S on),
-// which is all bmpc_set_transform would have scattered there.
+// which is all bmpc_set_transform would have scattered there.  opt: the plan's scene options or null
+// (the merge scene reads the disturbance only: its obstacle never chooses), e: the ego's index.
 __device__ __forceinline__ void merge_env_step_slab(const bmpc_merge_env_desc& env, const MergeRef& R, const Plan& P,
                                                     const Layout& L, int t, double* st, double* ws, const double* up,
-                                                    double* x, double* z, double* xr) {
+                                                    double* x, double* z, double* xr, const SceneOptions* opt, int e) {
   double* xf = ws + L.xform;
-  merge_env_step_ego(env, R, P.desc.bx, P.nFx, P.desc.dt, t, st, up, x, z, xr, xf + XF_S, xf + XF_BX);
+  merge_env_step_ego(env, R, P.desc.bx, P.nFx, P.desc.dt, t, st, up, x, z, xr, xf + XF_S, xf + XF_BX,
+                     scene_dist(opt), e);
   xf[XF_SON] = 1.0;
   xf[XF_BXSET] = 1.0;
 }
@@ -434,9 +436,9 @@ __device__ __attribute__((noinline)) void loop_merge_env_step(const bmpc_merge_e
                                                               const Plan& P, const Layout& L, int t, double* st,
                                                               double* ws, const double* up, double* x, double* z,
                                                               double* xr, double Jv, int status, int iters,
-                                                              double* stats) {
+                                                              double* stats, const SceneOptions* opt, int e) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, true, stats);
-  merge_env_step_slab(env, R, P, L, t, st, ws, up, x, z, xr);
+  merge_env_step_slab(env, R, P, L, t, st, ws, up, x, z, xr, opt, e);
 }
 
 // The quadruped loop's solve and scene step as calls (OSQP-class controllers: env_accumulate reads
@@ -450,9 +452,10 @@ __device__ __attribute__((noinline)) void loop_quad_env_step(const bmpc_quad_env
                                                              double* x, double* z, double* xr, double Jv, int status,
                                                              int iters, double* stats,
                                                              const bmpc_obstacle_sampling& smp, int e,
-                                                             const bmpc_obstacle_proposal* prop) {
+                                                             const SceneOptions* opt) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, false, stats);
-  quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr, &smp, e, prop);
+  quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr, &smp, e, scene_prop(opt),
+                    scene_dist(opt));
 }
 
 // Ego e's row r of the closed loops' recorder (bmpc_record.h), by the 64 lanes of one wave: the
@@ -497,8 +500,8 @@ __device__ __attribute__((noinline)) void loop_record_wide(double* upred, double
 // The scene of a k_loop (its kernel argument): one ego's scene step on lane 0, through an
 // out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
 // ego's transform slots, the quadruped scene neither.  The overtake and the quadruped scene carry the
-// plan's obstacle sampler (mode 0: none) and a pointer to its proposal (null: none); the merge scene's
-// obstacle never chooses.  kQp: the step's
+// plan's obstacle sampler (mode 0: none); the merge scene's obstacle never chooses.  All three carry
+// a pointer to the plan's scene options (null: none): the proposal and the disturbance.  kQp: the step's
 // solve is the OSQP-class controllers' solve_ego_qp (k_qp's) instead of the CVaR IPM.  kInlineIpm: the solve inlined into
 // the kernel as k_ipm / k_qp have it (the tree and scene steps stay calls) instead of a call of
 // its own -- as a callee the IPM's frame grows from k_ipm's ~590 to ~1,490 bytes per lane (merge
@@ -509,11 +512,11 @@ struct OvertakeScene {
   static constexpr bool kInlineIpm = false;
   bmpc_env_desc env;
   bmpc_obstacle_sampling smp;
-  const bmpc_obstacle_proposal* prop;
+  const SceneOptions* opt;
   __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
     loop_env_step(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, P.desc.mc,
-                  (int)blockIdx.x, prop);
+                  (int)blockIdx.x, opt);
   }
 };
 struct MergeScene {
@@ -521,9 +524,10 @@ struct MergeScene {
   static constexpr bool kInlineIpm = BMPC_MERGE_LOOP_INLINE_IPM != 0;
   bmpc_merge_env_desc env;
   MergeRef ref;
+  const SceneOptions* opt;
   __device__ void step(const Plan& P, const Layout& L, int t, double* st, bmpc_policy*, double* ws, const double* up,
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
-    loop_merge_env_step(env, ref, P, L, t, st, ws, up, x, z, xr, Jv, status, iters, stats);
+    loop_merge_env_step(env, ref, P, L, t, st, ws, up, x, z, xr, Jv, status, iters, stats, opt, (int)blockIdx.x);
   }
 };
 struct QuadScene {
@@ -531,10 +535,10 @@ struct QuadScene {
   static constexpr bool kInlineIpm = BMPC_QUAD_LOOP_INLINE_QP != 0;   // (both forms measured)
   bmpc_quad_env_desc env;
   bmpc_obstacle_sampling smp;
-  const bmpc_obstacle_proposal* prop;
+  const SceneOptions* opt;
   __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
-    loop_quad_env_step(env, P, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, (int)blockIdx.x, prop);
+    loop_quad_env_step(env, P, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, (int)blockIdx.x, opt);
   }
 };
 
@@ -635,7 +639,7 @@ struct SolveLaunch {
   const struct PhasedLaunch* ph = nullptr;   // tools-only builds (BMPC_WITH_PHASED, below)
   bmpc_loop_record rec = {};         // the fused closed loop's recorder (capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the fused closed loop's obstacle sampler (mode 0: none)
-  const bmpc_obstacle_proposal* prop = nullptr;   // ... and the plan's device copy of its proposal (null: none)
+  const SceneOptions* opt = nullptr;   // ... and the plan's device block of scene options (null: none)
 };
 using LaunchFn = hipError_t(const SolveLaunch&);
 

@@ -121,23 +121,39 @@ BMPC_HD int env_sampled_choice(const bmpc_obstacle_sampling& S, long long e, con
 }
 BMPC_HD bool env_samples(const bmpc_obstacle_sampling* smp) { return smp && smp->mode != BMPC_OBS_ARGMAX; }
 
+// What a plan has attached to its scenes beyond the sampler, as one device block behind one pointer
+// (null: nothing attached): the obstacle proposal (bmpc_set_obstacle_proposal; read only in the
+// sampler modes that need one, which the host admits only while one is attached) followed by the
+// actuation disturbance (bmpc_set_disturbance; law BMPC_DISTURB_NONE while none is attached).
+struct SceneOptions {
+  bmpc_obstacle_proposal prop;
+  bmpc_disturbance dist;
+};
+BMPC_HD const bmpc_obstacle_proposal* scene_prop(const SceneOptions* o) { return o ? &o->prop : nullptr; }
+BMPC_HD const bmpc_disturbance* scene_dist(const SceneOptions* o) { return o ? &o->dist : nullptr; }
+
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; pol: the
 // ego's m model policies (the lane-change target is re-targeted in place, update_backup);
 // u0: uPred[0] of the last solve (unused at t == 0); x_out, z_out, xref_out: the next
 // solve's inputs.  smp: the plan's obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the
 // reference's argmax rule), with mc, the plan's model constants, and e, the ego's index in the plan;
-// prop: the plan's obstacle proposal (read in modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT only).
+// prop: the plan's obstacle proposal (read in modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT only);
+// dist: the plan's actuation disturbance or null (bmpc_set_disturbance: the inputs post(t-1) applies,
+// rng_disturb_input; the row's ENV_UOBS keeps the nominal input).
 BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t, double* st,
                           bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
                           double* xref_out, const bmpc_obstacle_sampling* smp = nullptr,
                           const double* mc = nullptr, long long e = 0,
-                          const bmpc_obstacle_proposal* prop = nullptr) {
+                          const bmpc_obstacle_proposal* prop = nullptr,
+                          const bmpc_disturbance* dist = nullptr) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
-    double xp[4], zp[4];
-    step<Highway>(dt, x, u0, xp);
-    step<Highway>(dt, z, st + ENV_UOBS, zp);
+    double xp[4], zp[4], ue[2], uo[2];
+    rng_disturb_input(dist, true, e, t - 1, 2, u0, ue);
+    rng_disturb_input(dist, false, e, t - 1, 2, st + ENV_UOBS, uo);
+    step<Highway>(dt, x, ue, xp);
+    step<Highway>(dt, z, uo, zp);
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = xp[i], z[i] = zp[i];
   }

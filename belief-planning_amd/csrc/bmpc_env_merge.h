@@ -33,16 +33,21 @@ struct MergeRef {
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; bx_plan: the
 // plan's state bound (mpc.param.bx, nbx entries); u0: uPred[0] of the last solve (unused at
 // t == 0); x_out, z_out, xref_out: the next solve's inputs; S_out [4][4] and bx_out [nbx]: the
-// solve's state transformation and state bound (nbx >= 4 on the ramp's rule).
+// solve's state transformation and state bound (nbx >= 4 on the ramp's rule).  dist: the plan's
+// actuation disturbance or null (bmpc_set_disturbance, as in env_step_ego), with e, the ego's index
+// in the plan.
 BMPC_HD void merge_env_step_ego(const bmpc_merge_env_desc& E, const MergeRef& R, const double* bx_plan, int nbx,
                                 double dt, int t, double* st, const double* u0, double* x_out, double* z_out,
-                                double* xref_out, double* S_out, double* bx_out) {
+                                double* xref_out, double* S_out, double* bx_out,
+                                const bmpc_disturbance* dist = nullptr, long long e = 0) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
-    double xp[4], zp[4];
-    step<Highway>(dt, x, u0, xp);
-    step<Highway>(dt, z, st + ENV_UOBS, zp);
+    double xp[4], zp[4], ue[2], uo[2];
+    rng_disturb_input(dist, true, e, t - 1, 2, u0, ue);
+    rng_disturb_input(dist, false, e, t - 1, 2, st + ENV_UOBS, uo);
+    step<Highway>(dt, x, ue, xp);
+    step<Highway>(dt, z, uo, zp);
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = xp[i], z[i] = zp[i];
   }

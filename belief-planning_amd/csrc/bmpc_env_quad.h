@@ -42,17 +42,21 @@ BMPC_HD double quad_env_robot_col(const double* mc, double a0, double a1, double
 // model constants; pol: the ego's m model policies; u0: uPred[0] of the last solve (unused at
 // t == 0); x_out, z_out, xref_out: the next solve's inputs (3 doubles each).  smp: the plan's
 // obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the reference's rule); e: the ego's
-// index in the plan; prop: the plan's obstacle proposal (the weighted modes, bmpc_env.h).
+// index in the plan; prop: the plan's obstacle proposal (the weighted modes, bmpc_env.h); dist: the
+// plan's actuation disturbance or null (bmpc_set_disturbance, as in env_step_ego).
 BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, double dt, int N, int m, int t,
                                double* st, const bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
                                double* xref_out, const bmpc_obstacle_sampling* smp = nullptr, long long e = 0,
-                               const bmpc_obstacle_proposal* prop = nullptr) {
+                               const bmpc_obstacle_proposal* prop = nullptr,
+                               const bmpc_disturbance* dist = nullptr) {
   double* x = st + QENV_X;
   double* z = st + QENV_Z;
   if (t > 0) {   // post(t-1): robot.step of ego and obstacle
-    double xp[3], zp[3];
-    step<Quadruped>(dt, x, u0, xp);
-    step<Quadruped>(dt, z, st + QENV_UOBS, zp);
+    double xp[3], zp[3], ue[3], uo[3];
+    rng_disturb_input(dist, true, e, t - 1, 3, u0, ue);
+    rng_disturb_input(dist, false, e, t - 1, 3, st + QENV_UOBS, uo);
+    step<Quadruped>(dt, x, ue, xp);
+    step<Quadruped>(dt, z, uo, zp);
 #pragma unroll
     for (int i = 0; i < 3; ++i) x[i] = xp[i], z[i] = zp[i];
   }

@@ -37,26 +37,29 @@ static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, s
 }
 
 // one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve.  smp: the plan's
-// obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device, prop: the
-// plan's device copy of its obstacle proposal (null: none; read by the weighted modes only)
+// obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device, opt: the
+// plan's device block of scene options (null: none; bmpc_env.h SceneOptions -- the obstacle proposal,
+// read by the weighted modes only, and the actuation disturbance)
 __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, int t, int batch, double* scene,
                       bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
                       const int32_t* iters, int cvar, double* x, double* z, double* xref, double* stats,
-                      bmpc_obstacle_sampling smp, const double* mc, const bmpc_obstacle_proposal* prop) {
+                      bmpc_obstacle_sampling smp, const double* mc, const SceneOptions* opt) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   double* st = scene + (size_t)e * ENV_STRIDE;
   if (t > 0 && stats && J && status && iters)
     env_accumulate(st, J[e], status[e], iters[e], cvar != 0, stats + (size_t)e * ENVS_STRIDE);
   env_step_ego(E, dt, N, m, t, st, pol + (size_t)e * m, upred ? upred + (size_t)e * U * d : nullptr,
-               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e, prop);
+               x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e, scene_prop(opt),
+               scene_dist(opt));
 }
 
 // one thread per ego: the merge scene step (bmpc_env_merge.h) around the solve; S, bx and their
 // flags go straight into the ego's transform slots (no bmpc_set_transform before the solve)
 __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E, MergeRef R, int t, int batch,
                             double* scene, double* ws, const double* upred, const double* J, const int32_t* status,
-                            const int32_t* iters, double* x, double* z, double* xref, double* stats) {
+                            const int32_t* iters, double* x, double* z, double* xref, double* stats,
+                            const SceneOptions* opt) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   const Plan& P = B->P;
@@ -65,7 +68,7 @@ __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E,
   if (t > 0 && stats && J && status && iters)
     env_accumulate(st, J[e], status[e], iters[e], true, stats + (size_t)e * ENVS_STRIDE);
   merge_env_step_slab(E, R, P, L, t, st, ws + L.stride * (size_t)e, upred ? upred + (size_t)e * P.U * P.d : nullptr,
-                      x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4);
+                      x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, opt, e);
 }
 
 // one thread per ego: the quadruped scene step (bmpc_env_quad.h) around the solve of an OSQP-class
@@ -73,7 +76,7 @@ __global__ void k_env_merge(const Bundle* __restrict__ B, bmpc_merge_env_desc E,
 __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, int t, int batch, double* scene,
                            const bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
                            const int32_t* iters, double* x, double* z, double* xref, double* stats,
-                           bmpc_obstacle_sampling smp, const bmpc_obstacle_proposal* prop) {
+                           bmpc_obstacle_sampling smp, const SceneOptions* opt) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= batch) return;
   const Plan& P = B->P;
@@ -82,7 +85,7 @@ __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, i
     env_accumulate(st, J[e], status[e], iters[e], false, stats + (size_t)e * ENVS_STRIDE);
   quad_env_step_ego(E, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol + (size_t)e * P.m,
                     upred ? upred + (size_t)e * P.U * P.d : nullptr, x + (size_t)e * 3, z + (size_t)e * 3,
-                    xref + (size_t)e * 3, &smp, e, prop);
+                    xref + (size_t)e * 3, &smp, e, scene_prop(opt), scene_dist(opt));
 }
 
 // One wave per ego: step t's row of the closed loops' recorder after the per-step launches (run_loop)
@@ -540,11 +543,14 @@ struct bmpc_plan {
   int n_mref = 0;   // 0: no merge scene set
   bmpc_loop_record rec = {};   // the closed loops' recorder (bmpc_set_loop_record; capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the scenes' obstacle sampler (bmpc_set_obstacle_sampling; mode 0: none)
-  // the obstacle proposal (bmpc_set_obstacle_proposal): the host copy, and the device copy the scene
-  // kernels read through one pointer (allocated at the first attach; has_prop false: none attached)
+  // the obstacle proposal (bmpc_set_obstacle_proposal) and the actuation disturbance
+  // (bmpc_set_disturbance): the host copies, and the device block of both that the scene kernels read
+  // through one pointer (allocated at the first attach of either; has_prop / has_dist false: none
+  // attached -- the block's disturbance then has law BMPC_DISTURB_NONE)
   bmpc_obstacle_proposal prop = {};
-  bmpc_obstacle_proposal* d_prop = nullptr;
-  bool has_prop = false;
+  bmpc_disturbance dist = {};
+  SceneOptions* d_opt = nullptr;
+  bool has_prop = false, has_dist = false;
   uint64_t* d_rs = nullptr;   // bmpc_resample_device's scans (2 * batch uint64, allocated at the first call)
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
@@ -563,8 +569,24 @@ static int drain(bmpc_plan* pl) {
   return 0;
 }
 
-// the proposal pointer the scene kernels get: the plan's device copy, or null when none is attached
-static const bmpc_obstacle_proposal* scene_proposal(const bmpc_plan* pl) { return pl->has_prop ? pl->d_prop : nullptr; }
+// the options pointer the scene kernels get: the plan's device block, or null when neither a proposal
+// nor a disturbance is attached
+static const SceneOptions* scene_options(const bmpc_plan* pl) {
+  return pl->has_prop || pl->has_dist ? pl->d_opt : nullptr;
+}
+
+// the plan's host copies into its device block, allocated at the first call, after draining the
+// plan's streams: no scene step in flight reads the old block
+static int upload_scene_options(bmpc_plan* pl, const bmpc_obstacle_proposal& prop, const bmpc_disturbance& dist) {
+  HIPCHECK(hipSetDevice(pl->ctx->device));
+  if (const int rc = drain(pl)) return rc;
+  if (!pl->d_opt) HIPCHECK(hipMalloc(&pl->d_opt, sizeof(SceneOptions)));
+  SceneOptions h;
+  h.prop = prop;
+  h.dist = dist;
+  HIPCHECK(hipMemcpy(pl->d_opt, &h, sizeof(h), hipMemcpyHostToDevice));
+  return 0;
+}
 
 // "" when the plan's sampler is not in mode BMPC_OBS_SCRIPT or its script covers every epoch of the
 // closed-loop steps [t0, t0 + nsteps) (t0 >= 0, nsteps >= 1): checked on the host by every entry that
@@ -678,7 +700,7 @@ int bmpc_plan_destroy(bmpc_plan* pl) {
   hipFree(pl->d_scratch);
   hipFree(pl->d_lref);
   hipFree(pl->d_mref);
-  hipFree(pl->d_prop);
+  hipFree(pl->d_opt);
   hipFree(pl->d_rs);
   hipFree(pl->d_blk_lay);
   for (auto& e : pl->ev)
@@ -999,8 +1021,9 @@ extern "C++" {
 // (bmpc_set_loop_record) rides along either way: k_loop takes it as an argument; the per-step path
 // launches k_loop_record after each solve whose step lies in the window.  The plan's obstacle sampler
 // (bmpc_set_obstacle_sampling) reaches both paths: k_loop's scene argument carries it, and `step` is
-// the single-step entry point, which passes it to k_env / k_env_quad; the pointer to the plan's obstacle
-// proposal (bmpc_set_obstacle_proposal) travels beside it on both.
+// the single-step entry point, which passes it to k_env / k_env_quad; the pointer to the plan's scene
+// options -- its obstacle proposal (bmpc_set_obstacle_proposal) and its disturbance
+// (bmpc_set_disturbance) -- travels beside it on both, to the merge scene too.
 template <class Step, class Fused>
 static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_scene, double* d_upred,
                     double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
@@ -1024,7 +1047,7 @@ static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nst
   SolveLaunch a = solve_launch(pl, ch, s, d_x, d_z, d_xref, d_upred, nullptr, nullptr, d_J, d_status, d_iters);
   a.rec = pl->rec;
   a.smp = pl->smp;
-  a.prop = scene_proposal(pl);
+  a.opt = scene_options(pl);
   pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
   // (the whole fused launch is booked as the solver's time, none as the tree's)
   if (const int rc = timing_mark(pl, s, 0)) return rc;
@@ -1090,7 +1113,7 @@ int bmpc_env_step(bmpc_plan* pl, const bmpc_env_desc* env, int t, double* d_scen
   hipLaunchKernelGGL(k_env, dim3((pl->batch + 63) / 64), dim3(64), 0, s, *env, P.desc.dt, P.N, P.m, P.U, P.d, t,
                      pl->batch, d_scene, pl->d_pol, d_upred, d_J, d_status, d_iters,
                      P.desc.controller == BMPC_CTRL_CVAR ? 1 : 0, d_x, d_z, d_xref, d_stats, pl->smp,
-                     pl->d_bundle->P.desc.mc, scene_proposal(pl));
+                     pl->d_bundle->P.desc.mc, scene_options(pl));
   HIPCHECK(hipGetLastError());
   pl->pol_on_device = true;
   return 0;
@@ -1156,7 +1179,7 @@ int bmpc_merge_env_step(bmpc_plan* pl, int t, double* d_scene, const double* d_u
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env_merge, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, pl->menv,
                      MergeRef{pl->d_mref, pl->n_mref}, t, pl->batch, d_scene, pl->d_ws, d_upred, d_J, d_status, d_iters,
-                     d_x, d_z, d_xref, d_stats);
+                     d_x, d_z, d_xref, d_stats, scene_options(pl));
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1196,7 +1219,7 @@ int bmpc_quad_env_step(bmpc_plan* pl, const bmpc_quad_env_desc* env, int t, doub
   HIPCHECK(hipSetDevice(pl->ctx->device));
   hipStream_t s = plan_stream(pl, stream);
   hipLaunchKernelGGL(k_env_quad, dim3((pl->batch + 63) / 64), dim3(64), 0, s, pl->d_bundle, *env, t, pl->batch, d_scene,
-                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, pl->smp, scene_proposal(pl));
+                     pl->d_pol, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, pl->smp, scene_options(pl));
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1290,12 +1313,56 @@ int bmpc_set_obstacle_proposal(bmpc_plan* pl, const bmpc_obstacle_proposal* q) {
   bmpc_obstacle_proposal h = *q;
   for (int j = P.m; j < BMPC_MAX_M; ++j) h.tilt[j] = 1.0;   // (never read)
   if (h.script_epochs == 0) h.script = nullptr;
-  HIPCHECK(hipSetDevice(pl->ctx->device));
-  if (const int rc = drain(pl)) return rc;   // no scene step in flight reads the old copy
-  if (!pl->d_prop) HIPCHECK(hipMalloc(&pl->d_prop, sizeof(bmpc_obstacle_proposal)));
-  HIPCHECK(hipMemcpy(pl->d_prop, &h, sizeof(h), hipMemcpyHostToDevice));
+  if (const int rc = upload_scene_options(pl, h, pl->dist)) return rc;
   pl->prop = h;
   pl->has_prop = true;
+  return 0;
+}
+
+// "" for the plans one of the three scene entries accepts (bmpc_env_step, bmpc_set_merge_scene,
+// bmpc_quad_env_step)
+static std::string check_scene_plan(const Plan& P) {
+  if (P.desc.model == BMPC_MODEL_QUADRUPED) return check_quad_scene_plan(P);
+  if (P.desc.model == BMPC_MODEL_HIGHWAY_MERGE) {
+    if (P.desc.controller != BMPC_CTRL_CVAR || P.n != 4 || P.d != 2 || P.nFx != 4)
+      return "the merge scene needs a HIGHWAY_MERGE CVaR plan (n = 4, d = 2, nFx = 4)";
+    return "";
+  }
+  if (P.desc.model != BMPC_MODEL_HIGHWAY || P.n != 4 || P.d != 2)
+    return "the overtake scene needs a highway plan (n = 4, d = 2)";
+  return "";
+}
+
+int bmpc_set_disturbance(bmpc_plan* pl, const bmpc_disturbance* d) {
+  if (!pl) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (!d) {
+    // (the block stays allocated: a loop in flight may still read it; where an attached proposal keeps
+    // its pointer in use by the launches to come, the block's law is cleared)
+    if (pl->has_dist && pl->has_prop)
+      if (const int rc = upload_scene_options(pl, pl->prop, bmpc_disturbance{})) return rc;
+    pl->has_dist = false;
+    pl->dist = bmpc_disturbance{};
+    return 0;
+  }
+  if (d->law != BMPC_DISTURB_NONE && d->law != BMPC_DISTURB_IH4)
+    return fail(-22, "bmpc_set_disturbance: unknown law (BMPC_DISTURB_NONE or BMPC_DISTURB_IH4)");
+  if (d->ego_base < 0) return fail(-22, "bmpc_set_disturbance: ego_base must not be negative");
+  for (int v = 0; v < 2; ++v)
+    for (int c = 0; c < BMPC_MAX_D; ++c) {
+      const double sg = v == 0 ? d->sigma_ego[c] : d->sigma_obs[c];
+      const std::string name = std::string(v == 0 ? "sigma_ego[" : "sigma_obs[") + std::to_string(c) + "]";
+      if (!(std::isfinite(sg) && sg >= 0.0)) return fail(-22, "bmpc_set_disturbance: " + name + " must be finite and >= 0");
+      if (c >= P.d && sg != 0.0)
+        return fail(-22, "bmpc_set_disturbance: " + name + " must be 0: the plan's inputs have " + std::to_string(P.d) +
+                             " components");
+    }
+  if (const std::string e = check_scene_plan(P); !e.empty()) return fail(-22, "bmpc_set_disturbance: " + e);
+  bmpc_disturbance h = *d;
+  h.reserved = 0;
+  if (const int rc = upload_scene_options(pl, pl->prop, h)) return rc;
+  pl->dist = h;
+  pl->has_dist = true;
   return 0;
 }
 

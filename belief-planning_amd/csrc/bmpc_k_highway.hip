@@ -8,7 +8,7 @@ hipError_t launch_tree_highway(const SolveLaunch& a) { return launch_tree<Highwa
 hipError_t launch_solver_highway(const SolveLaunch& a) { return launch_solver<Highway, true>(a); }
 hipError_t launch_loop_highway(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
                                double* stats) {
-  return launch_loop<Highway>(a, OvertakeScene{env, a.smp, a.prop}, t0, nsteps, scene, stats);
+  return launch_loop<Highway>(a, OvertakeScene{env, a.smp, a.opt}, t0, nsteps, scene, stats);
 }
 
 }  // namespace dev

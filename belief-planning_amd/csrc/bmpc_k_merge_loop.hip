@@ -6,7 +6,7 @@ namespace dev {
 
 hipError_t launch_loop_merge(const SolveLaunch& a, const bmpc_merge_env_desc& env, const MergeRef& ref, int t0,
                              int nsteps, double* scene, double* stats) {
-  return launch_loop<HighwayMerge>(a, MergeScene{env, ref}, t0, nsteps, scene, stats);
+  return launch_loop<HighwayMerge>(a, MergeScene{env, ref, a.opt}, t0, nsteps, scene, stats);
 }
 
 }  // namespace dev

@@ -6,7 +6,7 @@ namespace dev {
 
 hipError_t launch_loop_quad(const SolveLaunch& a, const bmpc_quad_env_desc& env, int t0, int nsteps, double* scene,
                             double* stats) {
-  return launch_loop<Quadruped>(a, QuadScene{env, a.smp, a.prop}, t0, nsteps, scene, stats);
+  return launch_loop<Quadruped>(a, QuadScene{env, a.smp, a.opt}, t0, nsteps, scene, stats);
 }
 
 }  // namespace dev

@@ -1,19 +1,23 @@
-// bmpc_rng.h -- the closed loops' counter-based random draws (bmpc_set_obstacle_sampling).
+// bmpc_rng.h -- the closed loops' counter-based random draws (bmpc_set_obstacle_sampling,
+// bmpc_set_disturbance).
 //
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): a keyed
 // bijection of a 128-bit counter, no state.  A draw is addressed, never consumed -- counter
 //   {lo32(g), hi32(g), epoch, purpose},  key {lo32(seed), hi32(seed)},
 // g the ego's global index (the plan's ego_base + its ego e), epoch = t / hold, purpose 0 the
 // obstacle's backup policy -- so the launch path, the split of a loop over calls and the shard an
-// ego lives in cannot change it.  Plain integer arithmetic, the same on host and device;
-// bmpc/rng.py restates it in NumPy.
+// ego lives in cannot change it.  The actuation disturbance (rng_disturbance below) is addressed the
+// same way, by the step t itself and one purpose per vehicle and input component.  Plain integer
+// arithmetic, the same on host and device; bmpc/rng.py restates it in NumPy.
 #pragma once
 
 #include "bmpc_core.h"
 
 namespace bmpc {
 
-enum { RNG_PURPOSE_OBSTACLE_POLICY = 0 };   // other purposes are reserved
+// counter word 3: 0 the obstacle's policy, 1 the resampling draw (bmpc_resample.h), 8 + c / 12 + c
+// component c of the obstacle's / the ego's actuation disturbance (c < BMPC_MAX_D); 2-7 are reserved
+enum { RNG_PURPOSE_OBSTACLE_POLICY = 0, RNG_PURPOSE_DISTURB_OBSTACLE = 8, RNG_PURPOSE_DISTURB_EGO = 12 };
 
 // out = Philox4x32-10(counter c, key k)
 BMPC_HD void philox4x32_10(const uint32_t c[4], const uint32_t k[2], uint32_t out[4]) {
@@ -48,6 +52,40 @@ BMPC_HD double rng_draw(uint64_t seed, uint64_t g, uint32_t epoch, uint32_t purp
 }
 BMPC_HD double obstacle_uniform(uint64_t seed, uint64_t g, uint32_t epoch) {
   return rng_draw(seed, g, epoch, RNG_PURPOSE_OBSTACLE_POLICY);
+}
+
+// The actuation disturbance's variate (bmpc_set_disturbance, law BMPC_DISTURB_IH4): the centred sum
+// of the four output words, an exact integer |s| < 2^34, times sqrt(3) / 2^32 -- one rounding, so the
+// same double on host, device and in NumPy.  Irwin-Hall with four terms: mean 0, variance 1 - 2^-64,
+// kurtosis 2.7, |xi| <= 2 sqrt(3).
+BMPC_HD double rng_ih4(const uint32_t o[4]) {
+  const int64_t s = (int64_t)o[0] + (int64_t)o[1] + (int64_t)o[2] + (int64_t)o[3] - 2 * (int64_t)0xFFFFFFFFu;
+  return (double)s * 0x1.bb67ae8584caap-32;
+}
+// xi of (seed, global ego g, closed-loop step t) for one purpose (RNG_PURPOSE_DISTURB_* + component)
+BMPC_HD double rng_disturbance(uint64_t seed, uint64_t g, uint32_t t, uint32_t purpose) {
+  const uint32_t c[4] = {(uint32_t)g, (uint32_t)(g >> 32), t, purpose};
+  const uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  uint32_t o[4];
+  philox4x32_10(c, k, o);
+  return rng_ih4(o);
+}
+// The input a vehicle applies at step t under the disturbance D (null or law NONE: u itself):
+// out[c] = u[c] + sigma[c] * xi(g, t, purpose0 + c), the product rounded before it is added; a
+// component with sigma == 0 makes no draw and passes u[c] through.  ego: the ego's input (sigma_ego,
+// purposes 12 + c) or the obstacle's (sigma_obs, 8 + c); e: the ego's index in the plan; d <= BMPC_MAX_D.
+BMPC_HD void rng_disturb_input(const bmpc_disturbance* D, bool ego, long long e, int t, int d, const double* u,
+                               double* out) {
+  for (int c = 0; c < d; ++c) out[c] = u[c];
+  if (!D || D->law != BMPC_DISTURB_IH4) return;
+  const double* sigma = ego ? D->sigma_ego : D->sigma_obs;
+  const uint32_t purpose0 = ego ? RNG_PURPOSE_DISTURB_EGO : RNG_PURPOSE_DISTURB_OBSTACLE;
+  for (int c = 0; c < d; ++c)
+    if (sigma[c] != 0.0) {
+#pragma clang fp contract(off)
+      const double dv = sigma[c] * rng_disturbance(D->seed, (uint64_t)(D->ego_base + e), (uint32_t)t, purpose0 + c);
+      out[c] = u[c] + dv;
+    }
 }
 
 // Inverse CDF over m weights: p_j = w_j / sum with the sum taken in order j = 0, 1, ...; the

@@ -36,6 +36,8 @@
  *                         branch_eval's distribution instead of the reference's argmax rules)
  *   bmpc_set_obstacle_proposal   (an extension: the draw tilted per policy, or a prescribed choice
  *                         per ego and epoch, with a running log-weight in the scene row)
+ *   bmpc_set_disturbance         (an extension: an actuation disturbance on both vehicles' inputs
+ *                         in the scenes' Euler steps, drawn per step)
  *   bmpc_population_ancestors / bmpc_gather_egos / bmpc_resample_device   (an extension: resampling a
  *                         weighted population between loop segments, on the device)
  *
@@ -561,6 +563,56 @@ static_assert(sizeof(bmpc_obstacle_proposal) == 8 * BMPC_MAX_M + 16 && offsetof(
  * bmpc_set_obstacle_sampling in turn refuses modes 2 and 3 without a proposal and mode 3 without
  * a script. */
 int bmpc_set_obstacle_proposal(bmpc_plan* plan, const bmpc_obstacle_proposal* q);
+
+/* Process noise in the device closed loops: an actuation disturbance on the ego and on the obstacle,
+ * drawn per step.  Without it both vehicles execute their inputs exactly, so a controller is only
+ * ever tested against the model it plans with.  An extension: the reference's scenes have no noise.
+ *
+ * The law BMPC_DISTURB_IH4 is a unit-variance, bounded, near-Gaussian variate made of integers
+ * (csrc/bmpc_rng.h; bmpc/rng.py restates it), the same double on host, device and in NumPy:
+ *   o[0..3] = Philox4x32-10(counter {lo32(g), hi32(g), t, purpose}, key {lo32(seed), hi32(seed)})
+ *   s  = (int64)o0 + o1 + o2 + o3 - 2 (2^32 - 1)         exact, |s| < 2^34
+ *   xi = (double)s * 0x1.bb67ae8584caap-32               sqrt(3) / 2^32: one rounding
+ * (Irwin-Hall with four terms: mean 0, variance 1 - 2^-64, kurtosis 2.7, |xi| <= 2 sqrt(3)), with
+ * g = ego_base + e the ego's global index, t the closed-loop step whose input is disturbed and
+ * purpose = 8 + c for component c of the obstacle's input, 12 + c for the ego's (c < BMPC_MAX_D).
+ *
+ * It acts only in the Euler step post(t-1) of the three scenes: the ego moves with
+ * uPred[0][c] + sigma_ego[c] * xi(g, t-1, 12 + c), the obstacle with its chosen input
+ * + sigma_obs[c] * xi(g, t-1, 8 + c), the product rounded before it is added.  A component with
+ * sigma == 0 makes no draw.  The scene row's obstacle-input slot and the recorder's u column keep the
+ * nominal inputs; the collision rule, the obstacle's choice, the x_ref rules and BMPC_ENV_LOGW are
+ * untouched (the noise has the same law under the model and under a proposal), and nothing is
+ * clipped to the actuator bounds.  A draw is addressed by slot, so clones made by bmpc_gather_egos
+ * diverge by themselves. */
+enum { BMPC_DISTURB_NONE = 0, BMPC_DISTURB_IH4 = 1 };
+typedef struct {
+  int32_t  law, reserved;          /* BMPC_DISTURB_*; reserved is ignored                 */
+  uint64_t seed;
+  int64_t  ego_base;               /* >= 0, as in bmpc_obstacle_sampling                  */
+  double   sigma_ego[BMPC_MAX_D];  /* >= 0 and finite; 0 at the components >= d           */
+  double   sigma_obs[BMPC_MAX_D];
+} bmpc_disturbance;
+#ifdef __cplusplus
+static_assert(sizeof(bmpc_disturbance) == 24 + 16 * BMPC_MAX_D && offsetof(bmpc_disturbance, law) == 0 &&
+                  offsetof(bmpc_disturbance, seed) == 8 && offsetof(bmpc_disturbance, ego_base) == 16 &&
+                  offsetof(bmpc_disturbance, sigma_ego) == 24 &&
+                  offsetof(bmpc_disturbance, sigma_obs) == 24 + 8 * BMPC_MAX_D,
+              "bmpc_disturbance is 88 bytes: law 0, seed 8, ego_base 16, sigma_ego 24, sigma_obs 56");
+#endif
+
+/* Attach (a copy of *d: the plan keeps one on the host and one on the device, behind the proposal's,
+ * which the scene kernels read through the same pointer) or detach (d == NULL) the plan's
+ * disturbance.  Re-attaching waits for the plan's streams before the device copy is overwritten, so
+ * a loop already launched keeps what it was launched with; detaching leaves the device copy
+ * allocated (and, where an attached proposal keeps the pointer in use, clears its law the same
+ * way).  Obeyed by bmpc_loop_device, bmpc_merge_loop_device and bmpc_quad_loop_device on either
+ * launch path and by the single-step bmpc_env_step, bmpc_merge_env_step and bmpc_quad_env_step, so
+ * a manual loop gets the same bits.  With law BMPC_DISTURB_NONE, all sigmas
+ * zero or nothing attached every path computes the bits it computed without this entry.  -22 with a
+ * message for an unknown law, ego_base < 0, a negative or non-finite sigma, a non-zero sigma at a
+ * component >= d, and a plan that none of the three scene entries accepts. */
+int bmpc_set_disturbance(bmpc_plan* plan, const bmpc_disturbance* d);
 
 /* Resampling a weighted population between loop segments (sequential Monte Carlo / particle
  * splitting): egos of large weight are cloned into the slots of egos of negligible weight and every
