@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -22,6 +23,11 @@ def context(device: int = 0):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _vp(*ptrs):
+    """Device pointers and stream handles (integers; None or 0: absent) as a C entry point's arguments."""
+    return [C.c_void_p(p) if p else None for p in ptrs]
 
 
 SCENE_KINDS = {abi.MODEL_HIGHWAY: "overtake", abi.MODEL_HIGHWAY_MERGE: "merge", abi.MODEL_QUADRUPED: "quadruped"}
@@ -199,8 +205,7 @@ class BatchPlan:
         """Device-pointer variant (e.g. torch tensors' data_ptr()), asynchronous, enqueued on
         `stream` (a hipStream_t handle; None = the plan's own non-blocking stream, which is
         NOT ordered with the legacy default stream -- pass the caller's stream)."""
-        vp = [C.c_void_p(p) if p else None for p in (x_ptr, z_ptr, xref_ptr, upred_ptr, xpred_ptr,
-                                                     bw_ptr, J_ptr, status_ptr, iters_ptr, stream)]
+        vp = _vp(x_ptr, z_ptr, xref_ptr, upred_ptr, xpred_ptr, bw_ptr, J_ptr, status_ptr, iters_ptr, stream)
         check(lib().bmpc_solve_device(self._h, *vp), "bmpc_solve_device")
 
     def env_step_device(self, env: abi.EnvDesc, t: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr,
@@ -208,8 +213,7 @@ class BatchPlan:
         """One closed-loop sim_overtake step of every ego on the device (bmpc_env_step):
         Euler step with the last uPred[0], collision flag, obstacle backup choice, lane /
         lane-change-target bookkeeping and x_ref -> the next solve's x, z, xref.  Async."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr,
-                                                     x_ptr, z_ptr, xref_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr, x_ptr, z_ptr, xref_ptr, stats_ptr, stream)
         check(lib().bmpc_env_step(self._h, C.byref(env), int(t), *vp), "bmpc_env_step")
 
     def loop_device(self, env: abi.EnvDesc, t0: int, nsteps: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr,
@@ -217,8 +221,7 @@ class BatchPlan:
         """nsteps closed-loop steps of every ego (bmpc_loop_device): env_step_device(t) then
         solve_device for t = t0 .. t0+nsteps-1, the same results; one fused launch (k_loop) when
         the batch takes the one-wave IPM.  Async on `stream`."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
-                                                     iters_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr, iters_ptr, stats_ptr, stream)
         check(lib().bmpc_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_loop_device")
 
     def set_merge_scene(self, env: abi.MergeEnvDesc, grid, refY, refpsi):
@@ -234,8 +237,7 @@ class BatchPlan:
         """One closed-loop sim_merge step of every ego on the device (bmpc_merge_env_step): Euler
         steps, collision flag, lane flag, obstacle input -> the next solve's x, z, xref, and its S /
         bx in the plan's transform slots (no set_transform before solve_device).  Async."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr,
-                                                     x_ptr, z_ptr, xref_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr, x_ptr, z_ptr, xref_ptr, stats_ptr, stream)
         check(lib().bmpc_merge_env_step(self._h, int(t), *vp), "bmpc_merge_env_step")
 
     def merge_loop_device(self, t0: int, nsteps: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr,
@@ -243,8 +245,7 @@ class BatchPlan:
         """nsteps closed-loop sim_merge steps of every ego (bmpc_merge_loop_device):
         merge_env_step_device(t) then solve_device per step, the same results; one fused launch
         (k_loop) when the batch takes the one-wave IPM.  Async on `stream`."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
-                                                     iters_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr, iters_ptr, stats_ptr, stream)
         check(lib().bmpc_merge_loop_device(self._h, int(t0), int(nsteps), *vp), "bmpc_merge_loop_device")
 
     def quad_env_step_device(self, env: abi.QuadEnvDesc, t: int, scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr,
@@ -253,8 +254,7 @@ class BatchPlan:
         steps of both robots, the obstacle's backup choice from the clearance along the ego's
         predicted path, x_ref towards the scene's per-ego x_des -> the next solve's x, z, xref
         [batch][3].  QUADRUPED plans with an OSQP-class controller.  Async."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr,
-                                                     x_ptr, z_ptr, xref_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, J_ptr, status_ptr, iters_ptr, x_ptr, z_ptr, xref_ptr, stats_ptr, stream)
         check(lib().bmpc_quad_env_step(self._h, C.byref(env), int(t), *vp), "bmpc_quad_env_step")
 
     def quad_loop_device(self, env: abi.QuadEnvDesc, t0: int, nsteps: int, scene_ptr, upred_ptr, x_ptr, z_ptr,
@@ -262,9 +262,17 @@ class BatchPlan:
         """nsteps closed-loop main_quadruped steps of every ego (bmpc_quad_loop_device):
         quad_env_step_device(t) then solve_device per step, the same results; one fused launch
         (k_loop with the QP solver) unless BMPC_LOOP_FUSED=0.  Async on `stream`."""
-        vp = [C.c_void_p(p) if p else None for p in (scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr,
-                                                     iters_ptr, stats_ptr, stream)]
+        vp = _vp(scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr, iters_ptr, stats_ptr, stream)
         check(lib().bmpc_quad_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_quad_loop_device")
+
+    def _scene_loop(self):
+        """This plan's closed-loop entry for its model as f(t0, nsteps, *pointers): quad_loop_device
+        or loop_device with the scene's default constants, or merge_loop_device (set_merge_scene's)."""
+        if self.desc.model == abi.MODEL_QUADRUPED:
+            return functools.partial(self.quad_loop_device, abi.make_quad_env())
+        if self.desc.model == abi.MODEL_HIGHWAY_MERGE:
+            return self.merge_loop_device
+        return functools.partial(self.loop_device, abi.make_env())
 
     # ---- the closed loops' recorder ---------------------------------------------------------
     def set_loop_record(self, rec):

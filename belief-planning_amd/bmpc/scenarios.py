@@ -128,41 +128,97 @@ def sampled_overtake_population(B, steps, seed=0, device=0, record=False, obstac
     ego then has the trajectory it has in the unsharded run.  desc: another highway plan description
     than highway_desc().  Any draw can be audited on the host with bmpc.rng.obstacle_uniform(
     obstacle_seed, global ego, t // hold)."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
-    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
-    pl.set_policies(highway_policy_rows(tgt))
+    pl, scene0 = _seeded_plan("overtake", B, seed, device, ego_base, population, desc)
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
-    return _overtake_loop(pl, x, z, steps, record, device)
+    return _closed_loop(pl, scene0, steps, record, device)
 
 
-def _overtake_loop(pl, x, z, steps, record, device):
-    """`steps` closed-loop steps from t = 0 of the overtake plan `pl` (policies and obstacle rule set)
-    from the states x, z [B, 4]: the population entries' results; closes the plan."""
+def _overtake_scene(x, z):
+    """The overtake and merge scenes' initial state rows [B, ENV_STRIDE] (csrc/bmpc_env.h)."""
+    x = np.atleast_2d(np.asarray(x, float))
+    scene = np.zeros((x.shape[0], abi.ENV_STRIDE))
+    scene[:, abi.ENV_X:abi.ENV_X + 4] = x
+    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = np.atleast_2d(np.asarray(z, float))
+    return scene
+
+
+def _scene_desc(kind, desc=None):
+    """desc, or the description of scene `kind` ("overtake", "merge", "quadruped") with its defaults."""
+    if desc is not None:
+        return desc
+    return {"overtake": highway_desc, "merge": merge_desc, "quadruped": quadruped_desc}[kind]()
+
+
+def _scene_plan(kind, x, z, x_des=None, desc=None, device=0):
+    """The plan of scene `kind` ("overtake", "merge", "quadruped") for the egos of states x, z [B, n]
+    (quadruped: goals x_des) -- its description (desc=None: the scene's own), policies and, for the
+    merge, scene constants -- and the egos' initial scene rows [B, ENV_STRIDE]."""
+    from . import plan
+    B = len(x)
+    if kind == "overtake":
+        rows, scene0 = highway_policy_rows(xref_rule(x, z)[1]), _overtake_scene(x, z)
+    elif kind == "merge":
+        rows, scene0 = merge_policy_rows(B), _overtake_scene(x, z)
+    else:
+        rows, scene0 = quadruped_policy_rows(B), quad_scene(x, z, x_des)
+    pl = plan.BatchPlan(_scene_desc(kind, desc), B, device)
+    pl.set_policies(rows)
+    if kind == "merge":
+        pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
+    return pl, scene0
+
+
+def _seeded_plan(kind, B, seed, device, ego_base=0, population=None, desc=None):
+    """_scene_plan for rows [ego_base, ego_base + B) of the scene's seeded population: seeded_batch,
+    seeded_merge_batch, or seeded_quadruped_batch with seeded_quadruped_goals."""
+    total, rows = _shard_rows(B, ego_base, population)
+    x_des = None
+    if kind == "overtake":
+        x, z = seeded_batch(total, seed)[:2]
+    elif kind == "merge":
+        x, z = seeded_merge_batch(total, seed)
+    else:
+        x, z = seeded_quadruped_batch(total, seed)[:2]
+        x_des = seeded_quadruped_goals(total, seed)[rows]
+    return _scene_plan(kind, x[rows], z[rows], x_des, desc, device)
+
+
+_LOOP_BUFFERS = ("scene", "upred", "x", "z", "xref", "J", "status", "iters", "stats")   # the loop entries' order
+
+
+def _closed_loop(pl, scene0, steps, record, device, every=None, resample=None):
+    """`steps` closed-loop steps from t = 0 of the plan `pl` (policies, scene and options set) from the
+    scene rows scene0 [B, ENV_STRIDE], on one stream without a host synchronisation: the population
+    entries' results (stats, scene[, record]); closes the plan.  every: loop calls of `every` steps
+    with BatchPlan.resample(buffers, round = the step the next call starts at, **resample) between
+    them; then also the list of (ancestor, info) per resampling."""
     import torch
-    B = pl.batch
+    B, n, d = pl.batch, pl.desc.n, pl.desc.d
+    steps = int(steps)
+    every = steps if every is None else int(every)
     dev = torch.device("cuda", device)
     f64 = dict(dtype=torch.float64, device=dev)
-    scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
-    scene[:, abi.ENV_X:abi.ENV_X + 4] = torch.tensor(x, **f64)
-    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = torch.tensor(z, **f64)
-    up = torch.zeros((B, pl.U, 2), **f64)
-    J = torch.zeros(B, **f64)
-    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
-    tx, tz, tr = (torch.zeros((B, 4), **f64) for _ in range(3))
+    i32 = dict(dtype=torch.int32, device=dev)
+    b = dict(scene=torch.tensor(scene0, **f64), upred=torch.zeros((B, pl.U, d), **f64), x=torch.zeros((B, n), **f64),
+             z=torch.zeros((B, n), **f64), xref=torch.zeros((B, n), **f64), J=torch.zeros(B, **f64),
+             status=torch.zeros(B, **i32), iters=torch.zeros(B, **i32), stats=torch.zeros((B, abi.ENV_NSTAT), **f64))
     rec = _attach_record(pl, steps, record)
     torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
     stream = torch.cuda.Stream(dev)
-    pl.loop_device(abi.make_env(), 0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(),
-                   tr.data_ptr(), J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
+    loop = pl._scene_loop()
+    rounds = []
+    for t in ((0,) if resample is None else range(0, steps, every)):
+        if t > 0:
+            rounds.append(pl.resample(b, t, stream=stream.cuda_stream, **resample))
+        loop(t, min(every, steps - t), *(b[k].data_ptr() for k in _LOOP_BUFFERS), stream.cuda_stream)
     stream.synchronize()
-    out = stats.cpu().numpy(), scene.cpu().numpy()
+    out = b["stats"].cpu().numpy(), b["scene"].cpu().numpy()
     if rec is not None:
         out += (rec.host(),)
     pl.close()
-    return out
+    if resample is None:
+        return out
+    return out, [(a.cpu().numpy(), i.cpu().numpy()) for a, i in rounds]
 
 
 def merge_desc(N=40, NB=1, N_lane=2, am=7.0, rm=0.3, L=4.0, W=2.5, s1=2.0, ralpha=0.1):
@@ -212,40 +268,8 @@ def merge_population(B, steps, seed=0, device=0, record=False):
     distributed.episode_stats takes; a step's solve is booked by the next step, so they cover
     steps - 1 solves) and the final scene [B, ENV_STRIDE]; with `record` (overtake_population's)
     also the per-step record on the host."""
-    from . import plan
-    x, z = seeded_merge_batch(B, seed)
-    pl = plan.BatchPlan(merge_desc(), B, device)
-    pl.set_policies(merge_policy_rows(B))
-    pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
-    return _merge_loop(pl, x, z, steps, record, device)
-
-
-def _merge_loop(pl, x, z, steps, record, device):
-    """`steps` closed-loop steps from t = 0 of the merge plan `pl` (policies and scene set) from the
-    states x, z [B, 4]: the population entries' results; closes the plan."""
-    import torch
-    B = pl.batch
-    dev = torch.device("cuda", device)
-    f64 = dict(dtype=torch.float64, device=dev)
-    scene = torch.zeros((B, abi.ENV_STRIDE), **f64)
-    scene[:, abi.ENV_X:abi.ENV_X + 4] = torch.tensor(x, **f64)
-    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = torch.tensor(z, **f64)
-    up = torch.zeros((B, pl.U, 2), **f64)
-    J = torch.zeros(B, **f64)
-    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
-    tx, tz, tr = (torch.zeros((B, 4), **f64) for _ in range(3))
-    rec = _attach_record(pl, steps, record)
-    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
-    stream = torch.cuda.Stream(dev)
-    pl.merge_loop_device(0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(), tr.data_ptr(),
-                         J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
-    stream.synchronize()
-    out = stats.cpu().numpy(), scene.cpu().numpy()
-    if rec is not None:
-        out += (rec.host(),)
-    pl.close()
-    return out
+    pl, scene0 = _seeded_plan("merge", B, seed, device)
+    return _closed_loop(pl, scene0, steps, record, device)
 
 
 def quadruped_desc(N=25, NB=2, vxm=0.2, vym=0.1, rm=0.5, dt=0.2, L1=0.5, W1=0.3, L2=1.0, W2=0.6,
@@ -314,40 +338,9 @@ def sampled_quadruped_population(B, steps, seed=0, device=0, record=False, obsta
     """quadruped_population with the sampled obstacle: sampled_overtake_population's arguments and
     sharding rule (rows ego_base .. ego_base + B - 1 of seeded_quadruped_batch(population, seed) and
     of seeded_quadruped_goals; a sharded run passes ego_base = distributed.shard(...)[0])."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
-    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
-    pl.set_policies(quadruped_policy_rows(B))
+    pl, scene0 = _seeded_plan("quadruped", B, seed, device, ego_base, population, desc)
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
-    return _quadruped_loop(pl, quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), steps, record, device)
-
-
-def _quadruped_loop(pl, scene0, steps, record, device):
-    """`steps` closed-loop steps from t = 0 of the quadruped plan `pl` (policies and obstacle rule set)
-    from the scene rows scene0 [B, ENV_STRIDE] (quad_scene): the population entries' results; closes
-    the plan."""
-    import torch
-    B = pl.batch
-    dev = torch.device("cuda", device)
-    f64 = dict(dtype=torch.float64, device=dev)
-    scene = torch.tensor(scene0, **f64)
-    up = torch.zeros((B, pl.U, 3), **f64)
-    J = torch.zeros(B, **f64)
-    st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-    stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
-    tx, tz, tr = (torch.zeros((B, 3), **f64) for _ in range(3))
-    rec = _attach_record(pl, steps, record)
-    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
-    stream = torch.cuda.Stream(dev)
-    pl.quad_loop_device(abi.make_quad_env(), 0, steps, scene.data_ptr(), up.data_ptr(), tx.data_ptr(), tz.data_ptr(),
-                        tr.data_ptr(), J.data_ptr(), st.data_ptr(), it.data_ptr(), stats.data_ptr(), stream.cuda_stream)
-    stream.synchronize()
-    out = stats.cpu().numpy(), scene.cpu().numpy()
-    if rec is not None:
-        out += (rec.host(),)
-    pl.close()
-    return out
+    return _closed_loop(pl, scene0, steps, record, device)
 
 
 def _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base):
@@ -383,63 +376,31 @@ def weighted_overtake_population(B, steps, seed=0, device=0, record=False, obsta
     realised choice sequence (the scene's abi.ENV_LOGW column, which starts at 0); with `record` also
     the record, whose `logw` column holds the weight's history.  montecarlo.estimate(f, logw) is the
     estimate of E_p[f] with its standard error."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
-    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
-    pl.set_policies(highway_policy_rows(tgt))
+    pl, scene0 = _seeded_plan("overtake", B, seed, device, ego_base, population, desc)
     _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
-    return _with_logw(_overtake_loop(pl, x, z, steps, record, device))
+    return _with_logw(_closed_loop(pl, scene0, steps, record, device))
 
 
 def weighted_quadruped_population(B, steps, seed=0, device=0, record=False, obstacle_seed=0, hold=1, ego_base=0,
                                   population=None, desc=None, tilt=None):
     """sampled_quadruped_population under importance sampling: weighted_overtake_population's
     arguments and results (sharding by ego_base = distributed.shard(...)[0])."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
-    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
-    pl.set_policies(quadruped_policy_rows(B))
+    pl, scene0 = _seeded_plan("quadruped", B, seed, device, ego_base, population, desc)
     _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
-    scene0 = quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows])
-    return _with_logw(_quadruped_loop(pl, scene0, steps, record, device))
+    return _with_logw(_closed_loop(pl, scene0, steps, record, device))
 
 
-def _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record, device):
-    """`steps` closed-loop steps from t = 0 of the overtake or quadruped plan `pl` in loop calls of
-    `resample_every` steps with BatchPlan.resample (round = the step t the next call starts at)
-    between them, all on one stream without a host synchronisation; closes the plan.  Returns
-    (stats, scene[, record]) and the list of (ancestor, info) per resampling."""
-    import torch
-    steps, every = int(steps), int(resample_every)
-    if every < 1 or every % int(hold):
+def _resampled(kind, B, steps, resample_every, ess_fraction, resample_seed, tilt, seed, device, record, obstacle_seed,
+               hold, ego_base, population, desc):
+    """The resampled_*_population entries: the weighted population of scene `kind` in loop calls of
+    `resample_every` steps with BatchPlan.resample between them."""
+    if int(resample_every) < 1 or int(resample_every) % int(hold):
         raise ValueError(f"resample_every must be a positive multiple of hold = {hold}")
-    B, n, d = pl.batch, pl.desc.n, pl.desc.d
-    quad = pl.desc.model == abi.MODEL_QUADRUPED
-    dev = torch.device("cuda", device)
-    f64 = dict(dtype=torch.float64, device=dev)
-    b = dict(scene=torch.tensor(scene0, **f64), upred=torch.zeros((B, pl.U, d), **f64), x=torch.zeros((B, n), **f64),
-             z=torch.zeros((B, n), **f64), xref=torch.zeros((B, n), **f64), J=torch.zeros(B, **f64),
-             status=torch.zeros(B, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev),
-             stats=torch.zeros((B, abi.ENV_NSTAT), **f64))
-    rec = _attach_record(pl, steps, record)
-    torch.cuda.synchronize(dev)          # the buffers are written before the loop's stream starts
-    stream = torch.cuda.Stream(dev)
-    env = abi.make_quad_env() if quad else abi.make_env()
-    loop = pl.quad_loop_device if quad else pl.loop_device
-    rounds = []
-    for t in range(0, steps, every):
-        if t > 0:
-            rounds.append(pl.resample(b, t, resample_seed, ess_fraction, ego_base, stream.cuda_stream))
-        loop(env, t, min(every, steps - t), *(b[k].data_ptr() for k in ("scene", "upred", "x", "z", "xref", "J", "status",
-                                                                      "iters", "stats")), stream.cuda_stream)
-    stream.synchronize()
-    out = b["stats"].cpu().numpy(), b["scene"].cpu().numpy()
-    if rec is not None:
-        out += (rec.host(),)
-    pl.close()
-    return out, [(a.cpu().numpy(), i.cpu().numpy()) for a, i in rounds]
+    pl, scene0 = _seeded_plan(kind, B, seed, device, ego_base, population, desc)
+    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
+    out, rounds = _closed_loop(pl, scene0, steps, record, device, every=resample_every,
+                               resample=dict(seed=resample_seed, ess_fraction=ess_fraction, ego_base=ego_base))
+    return _with_logw(out) + (rounds,)
 
 
 def resampled_overtake_population(B, steps, resample_every, ess_fraction=0.5, resample_seed=0, tilt=None, seed=0,
@@ -456,17 +417,8 @@ def resampled_overtake_population(B, steps, resample_every, ess_fraction=0.5, re
     addressed by slot and montecarlo.lineage(ancestors) tells which slot a final ego lived in.  A
     sharded run (ego_base = distributed.shard(...)[0]) resamples every shard by itself: a shard's mean
     weight carries its mass, and montecarlo.reduce_terms over the shards stays the plain estimate."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
-    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
-    pl.set_policies(highway_policy_rows(tgt))
-    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
-    scene0 = np.zeros((B, abi.ENV_STRIDE))
-    scene0[:, abi.ENV_X:abi.ENV_X + 4], scene0[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
-    out, rounds = _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record,
-                                  device)
-    return _with_logw(out) + (rounds,)
+    return _resampled("overtake", B, steps, resample_every, ess_fraction, resample_seed, tilt, seed, device, record,
+                      obstacle_seed, hold, ego_base, population, desc)
 
 
 def resampled_quadruped_population(B, steps, resample_every, ess_fraction=0.5, resample_seed=0, tilt=None, seed=0,
@@ -475,16 +427,8 @@ def resampled_quadruped_population(B, steps, resample_every, ess_fraction=0.5, r
     """weighted_quadruped_population with the population resampled between loop segments:
     resampled_overtake_population's arguments and results (a sharded run, ego_base =
     distributed.shard(...)[0], resamples every shard by itself)."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
-    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
-    pl.set_policies(quadruped_policy_rows(B))
-    _attach_tilt(pl, tilt, obstacle_seed, hold, ego_base)
-    scene0 = quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows])
-    out, rounds = _resampled_loop(pl, scene0, steps, resample_every, ess_fraction, resample_seed, hold, ego_base, record,
-                                  device)
-    return _with_logw(out) + (rounds,)
+    return _resampled("quadruped", B, steps, resample_every, ess_fraction, resample_seed, tilt, seed, device, record,
+                      obstacle_seed, hold, ego_base, population, desc)
 
 
 def enumerated_overtake_population(x0, z0, epochs, hold, device=0, record=False, desc=None):
@@ -494,30 +438,25 @@ def enumerated_overtake_population(x0, z0, epochs, hold, device=0, record=False,
     the statistics rows, the final scene, the path log-probabilities logp [m ** epochs] under the
     model's branch distribution (they sum to one: montecarlo.exact_expectation gives exact closed-loop
     expectations over the scenario tree) and the script; with `record` also the record."""
-    from . import plan
-    desc = highway_desc() if desc is None else desc
-    B = int(desc.m) ** int(epochs)
-    x = np.tile(np.asarray(x0, float).reshape(1, 4), (B, 1))
-    z = np.tile(np.asarray(z0, float).reshape(1, 4), (B, 1))
-    pl = plan.BatchPlan(desc, B, device)
-    pl.set_policies(highway_policy_rows(xref_rule(x, z)[1]))
-    script = _attach_script(pl, int(desc.m), int(epochs), hold)
-    out = _with_logw(_overtake_loop(pl, x, z, int(epochs) * int(hold), record, device))
-    return out[:3] + (script,) + out[3:]
+    return _enumerated("overtake", x0, z0, None, epochs, hold, device, record, desc)
 
 
 def enumerated_quadruped_population(x0, z0, x_des, epochs, hold, device=0, record=False, desc=None):
     """enumerated_overtake_population for the quadruped scene: one initial state (x0, z0 [3]) and goal
     x_des [3] against all m ** epochs choice sequences."""
-    from . import plan
-    desc = quadruped_desc() if desc is None else desc
-    B = int(desc.m) ** int(epochs)
-    x = np.tile(np.asarray(x0, float).reshape(1, 3), (B, 1))
-    pl = plan.BatchPlan(desc, B, device)
-    pl.set_policies(quadruped_policy_rows(B))
-    script = _attach_script(pl, int(desc.m), int(epochs), hold)
-    scene0 = quad_scene(x, np.asarray(z0, float).reshape(1, 3), np.asarray(x_des, float).reshape(1, 3))
-    out = _with_logw(_quadruped_loop(pl, scene0, int(epochs) * int(hold), record, device))
+    return _enumerated("quadruped", x0, z0, x_des, epochs, hold, device, record, desc)
+
+
+def _enumerated(kind, x0, z0, x_des, epochs, hold, device, record, desc):
+    """The enumerated_*_population entries: m ** epochs copies of one state of scene `kind`, one per
+    obstacle choice sequence."""
+    desc = _scene_desc(kind, desc)
+    m, epochs, n = int(desc.m), int(epochs), int(desc.n)
+    x, z = (np.tile(np.asarray(a, float).reshape(1, n), (m ** epochs, 1)) for a in (x0, z0))
+    x_des = None if x_des is None else np.asarray(x_des, float).reshape(1, n)
+    pl, scene0 = _scene_plan(kind, x, z, x_des, desc, device)
+    script = _attach_script(pl, m, epochs, hold)
+    out = _with_logw(_closed_loop(pl, scene0, epochs * int(hold), record, device))
     return out[:3] + (script,) + out[3:]
 
 
@@ -559,14 +498,10 @@ def disturbed_overtake_population(B, steps, sigma_ego=None, sigma_obs=None, dist
     (ego_base = distributed.shard(...)[0]): each ego has the trajectory it has in the unsharded run.
     The record's u and the scene's obstacle input are the nominal inputs; the applied ones are
     nominal + sigma * bmpc.rng.disturbance(...)."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _, tgt = (a[rows] for a in seeded_batch(total, seed))
-    pl = plan.BatchPlan(highway_desc() if desc is None else desc, B, device)
-    pl.set_policies(highway_policy_rows(tgt))
+    pl, scene0 = _seeded_plan("overtake", B, seed, device, ego_base, population, desc)
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
     _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
-    return _overtake_loop(pl, x, z, steps, record, device)
+    return _closed_loop(pl, scene0, steps, record, device)
 
 
 def disturbed_merge_population(B, steps, sigma_ego=None, sigma_obs=None, disturbance_seed=0, seed=0, device=0,
@@ -575,14 +510,9 @@ def disturbed_merge_population(B, steps, sigma_ego=None, sigma_obs=None, disturb
     the merge scene's first source of randomness beyond its initial states.  The B egos are rows
     ego_base .. ego_base + B - 1 of seeded_merge_batch(population, seed) and draw as those global
     egos."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z = (a[rows] for a in seeded_merge_batch(total, seed))
-    pl = plan.BatchPlan(merge_desc(), B, device)
-    pl.set_policies(merge_policy_rows(B))
-    pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
+    pl, scene0 = _seeded_plan("merge", B, seed, device, ego_base, population)
     _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
-    return _merge_loop(pl, x, z, steps, record, device)
+    return _closed_loop(pl, scene0, steps, record, device)
 
 
 def disturbed_quadruped_population(B, steps, sigma_ego=None, sigma_obs=None, disturbance_seed=0, seed=0, device=0,
@@ -590,11 +520,7 @@ def disturbed_quadruped_population(B, steps, sigma_ego=None, sigma_obs=None, dis
                                    desc=None):
     """sampled_quadruped_population under process noise: disturbed_overtake_population's arguments,
     the sigmas those of (vx, vy, yaw rate)."""
-    from . import plan
-    total, rows = _shard_rows(B, ego_base, population)
-    x, z, _ = (a[rows] for a in seeded_quadruped_batch(total, seed))
-    pl = plan.BatchPlan(quadruped_desc() if desc is None else desc, B, device)
-    pl.set_policies(quadruped_policy_rows(B))
+    pl, scene0 = _seeded_plan("quadruped", B, seed, device, ego_base, population, desc)
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
     _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
-    return _quadruped_loop(pl, quad_scene(x, z, seeded_quadruped_goals(total, seed)[rows]), steps, record, device)
+    return _closed_loop(pl, scene0, steps, record, device)

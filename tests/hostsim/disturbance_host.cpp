@@ -2,83 +2,16 @@
 // rng_ih4 / rng_disturbance / rng_disturb_input and the three scene functions' post(t-1);
 // bmpc_set_disturbance).
 //
-// Two builds of this one file (tests/test_disturbance.py): a stand-alone program under the address
-// and undefined-behaviour sanitizers -- main() below: the variate's known answers, its two extremes,
-// 64-bit egos and seeds, sigma = 0 --, and a shared library whose `dh_*` symbols let the CPU tests
-// drive the draws and the three scene functions with a disturbance.  Never loaded by the
-// belief-planning_amd package.
+// A stand-alone program under the address and undefined-behaviour sanitizers
+// (tests/test_disturbance.py): the variate's known answers, its two extremes, 64-bit egos and seeds,
+// sigma = 0.  The CPU tests drive the draws and the three scene functions with a disturbance through
+// tests/hostsim/scene_host.cpp.  Never loaded by the belief-planning_amd package.
 #include <stdio.h>
 
 #include "bmpc_env_merge.h"
 #include "bmpc_env_quad.h"
 
 using namespace bmpc;
-
-extern "C" {
-
-// out[i] = xi(seed[i], ego[i], step[i], purpose[i])
-void dh_xi(int n, const uint64_t* seed, const uint64_t* ego, const uint32_t* step, const uint32_t* purpose,
-           double* out) {
-  for (int i = 0; i < n; ++i) out[i] = rng_disturbance(seed[i], ego[i], step[i], purpose[i]);
-}
-
-// One overtake scene step of `batch` egos as k_env runs it (no statistics, the argmax obstacle).
-// legacy != 0 calls the scene function with the argument list it had before the disturbance.
-int dh_env_step(const bmpc_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch, double* scene,
-                bmpc_policy* pol, const double* upred, int upred_stride, double* x, double* z, double* xref,
-                const bmpc_disturbance* dist, int legacy) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    if (legacy)
-      env_step_ego(*env, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                   xref + (size_t)e * 4, nullptr, mc, e, nullptr);
-    else
-      env_step_ego(*env, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                   xref + (size_t)e * 4, nullptr, mc, e, nullptr, dist);
-  }
-  return 0;
-}
-
-// ... one merge scene step, as k_env_merge runs it (ref = grid | refY | refpsi; S [batch][16] and
-// bx [batch][nbx] stand in for the egos' transform slots)
-int dh_merge_env_step(const bmpc_merge_env_desc* env, int nref, const double* ref, const double* bx_plan, int nbx,
-                      double dt, int t, int batch, double* scene, const double* upred, int upred_stride, double* x,
-                      double* z, double* xref, double* S, double* bx, const bmpc_disturbance* dist, int legacy) {
-  const MergeRef R{ref, nref};
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    if (legacy)
-      merge_env_step_ego(*env, R, bx_plan, nbx, dt, t, st, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                         xref + (size_t)e * 4, S + (size_t)e * 16, bx + (size_t)e * nbx);
-    else
-      merge_env_step_ego(*env, R, bx_plan, nbx, dt, t, st, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                         xref + (size_t)e * 4, S + (size_t)e * 16, bx + (size_t)e * nbx, dist, e);
-  }
-  return 0;
-}
-
-// ... and one quadruped scene step, as k_env_quad runs it
-int dh_quad_env_step(const bmpc_quad_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch,
-                     double* scene, const bmpc_policy* pol, const double* upred, int upred_stride, double* x,
-                     double* z, double* xref, const bmpc_disturbance* dist, int legacy) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    if (legacy)
-      quad_env_step_ego(*env, mc, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 3, z + (size_t)e * 3,
-                        xref + (size_t)e * 3, nullptr, e, nullptr);
-    else
-      quad_env_step_ego(*env, mc, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 3, z + (size_t)e * 3,
-                        xref + (size_t)e * 3, nullptr, e, nullptr, dist);
-  }
-  return 0;
-}
-
-}  // extern "C"
 
 static int failures = 0;
 #define CHECK(c)                                           \

@@ -1,68 +1,20 @@
 // obstacle_proposal_host.cpp -- TEST-ONLY host build of the weighted obstacle modes (the tilted and the
 // scripted rule of csrc/bmpc_env.h / bmpc_env_quad.h; bmpc_set_obstacle_proposal).
 //
-// Two builds of this one file (tests/test_obstacle_proposal.py): a stand-alone program under the
-// address and undefined-behaviour sanitizers -- main() below: a tilt of ones against mode 1, the
-// log-weight of a tilted and of a scripted choice, the script's clamps at a table of exactly its
-// size, the epochs' untouched steps, and whole scene steps of both scenes in both modes --, and a
-// shared library whose `op_*` symbols let the CPU tests drive the two scene functions with a sampler
-// and a proposal.  Never loaded by the belief-planning_amd package.
+// A stand-alone program under the address and undefined-behaviour sanitizers
+// (tests/test_obstacle_proposal.py): a tilt of ones against mode 1, the log-weight of a tilted and of
+// a scripted choice, the script's clamps at a table of exactly its size, the epochs' untouched steps,
+// and whole scene steps of both scenes in both modes through scene_host.h's wrappers -- the ones the
+// CPU tests drive as a shared library (tests/hostsim/scene_host.cpp).  Never loaded by the
+// belief-planning_amd package.
 #include <math.h>
 #include <stdio.h>
 
 #include <vector>
 
-#include "bmpc_env_quad.h"
+#include "scene_host.h"
 
 using namespace bmpc;
-
-extern "C" {
-
-// One overtake scene step of `batch` egos as k_env runs it (no statistics): smp and prop as the
-// kernel gets them (prop may be null in modes 0 and 1).
-int op_env_step(const bmpc_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch, double* scene,
-                bmpc_policy* pol, const double* upred, int upred_stride, double* x, double* z, double* xref,
-                const bmpc_obstacle_sampling* smp, const bmpc_obstacle_proposal* prop) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  if (smp && smp->mode >= BMPC_OBS_SAMPLE_TILTED && !prop) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    env_step_ego(*env, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                 xref + (size_t)e * 4, smp, mc, e, prop);
-  }
-  return 0;
-}
-
-// ... and one quadruped scene step, as k_env_quad runs it
-int op_quad_env_step(const bmpc_quad_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch,
-                     double* scene, const bmpc_policy* pol, const double* upred, int upred_stride, double* x,
-                     double* z, double* xref, const bmpc_obstacle_sampling* smp, const bmpc_obstacle_proposal* prop) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  if (smp && smp->mode >= BMPC_OBS_SAMPLE_TILTED && !prop) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    quad_env_step_ego(*env, mc, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 3, z + (size_t)e * 3,
-                      xref + (size_t)e * 3, smp, e, prop);
-  }
-  return 0;
-}
-
-// the model weights w [batch][m] the rule forms at the states x, z [batch][n] under pol [batch][m]
-void op_weights(int quadruped, const double* mc, double dt, int N, int m, int batch, const bmpc_policy* pol,
-                const double* x, const double* z, double* w) {
-  const int n = quadruped ? 3 : 4;
-  for (int e = 0; e < batch; ++e)
-    for (int j = 0; j < m; ++j) {
-      const bmpc_policy* p = pol + (size_t)e * m;
-      const double *xe = x + (size_t)e * n, *ze = z + (size_t)e * n;
-      w[(size_t)e * m + j] = quadruped ? Quadruped::prob_weight(mc, Quadruped::bf_traj(mc, dt, N, p[0], p[j], xe, ze))
-                                       : Highway::prob_weight(mc, Highway::bf_traj(mc, dt, N, p[0], p[j], xe, ze));
-    }
-}
-
-}  // extern "C"
 
 static int failures = 0;
 #define CHECK(c)                                           \
@@ -174,10 +126,11 @@ int main() {
       }
       std::vector<double> xo(batch * 4), zo(batch * 4), xr(batch * 4), up(batch * 3, 0.05);
       for (int t = 0; t < steps; ++t) {
-        CHECK(op_env_step(&E, mc, 0.1, 6, 3, t, batch, scene.data(), p.data(), t ? up.data() : nullptr, 3, xo.data(),
-                          zo.data(), xr.data(), &S, &q) == 0);
-        CHECK(op_quad_env_step(&QE, qmc, 0.2, 6, 2, t, batch, qscene.data(), qp.data(), t ? up.data() : nullptr, 3,
-                               xo.data(), zo.data(), xr.data(), &S, &q) == 0);
+        CHECK(sh_env_step(&E, mc, 0.1, 6, 3, t, batch, scene.data(), p.data(), t ? up.data() : nullptr, 3, xo.data(),
+                          zo.data(), xr.data(), &S, &q, nullptr, 0) == 0);
+        CHECK(sh_quad_env_step(&QE, qmc, 0.2, 6, 2, t, batch, qscene.data(), qp.data(), t ? up.data() : nullptr, 3,
+                               nullptr, nullptr, nullptr, xo.data(), zo.data(), xr.data(), nullptr, &S, &q, nullptr,
+                               0) == 0);
         for (int e = 0; e < batch; ++e) {
           const double c = scene[e * ENV_STRIDE + ENV_OBSPOL], qc = qscene[e * ENV_STRIDE + ENV_OBSPOL];
           CHECK(c >= 0 && c <= 2 && qc >= 0 && qc <= 1);
@@ -197,10 +150,10 @@ int main() {
     for (int i = 0; i < 4; ++i) scene[ENV_X + i] = x[i], scene[ENV_Z + i] = z[i];
     scene[ENV_LOGW] = -7777.25;
     bmpc_policy p1[3] = {pol[0], pol[1], pol[2]};
-    CHECK(op_env_step(&E, mc, 0.1, 6, 3, 0, 1, scene.data(), p1, nullptr, 0, xo.data(), zo.data(), xr.data(), &S1,
-                      nullptr) == 0);
-    CHECK(op_env_step(&E, mc, 0.1, 6, 3, 0, 1, scene.data(), p1, nullptr, 0, xo.data(), zo.data(), xr.data(), nullptr,
-                      &q) == 0);
+    CHECK(sh_env_step(&E, mc, 0.1, 6, 3, 0, 1, scene.data(), p1, nullptr, 0, xo.data(), zo.data(), xr.data(), &S1,
+                      nullptr, nullptr, 0) == 0);
+    CHECK(sh_env_step(&E, mc, 0.1, 6, 3, 0, 1, scene.data(), p1, nullptr, 0, xo.data(), zo.data(), xr.data(), nullptr,
+                      &q, nullptr, 0) == 0);
     CHECK(scene[ENV_LOGW] == -7777.25);
   }
   if (failures) return 1;

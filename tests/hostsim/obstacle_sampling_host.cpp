@@ -1,66 +1,15 @@
 // obstacle_sampling_host.cpp -- TEST-ONLY host build of the sampled obstacle (csrc/bmpc_rng.h and the
 // sampled rule of csrc/bmpc_env.h / bmpc_env_quad.h; bmpc_set_obstacle_sampling).
 //
-// Two builds of this one file (tests/test_obstacle_sampling.py): a stand-alone program under the
-// address and undefined-behaviour sanitizers -- main() below: the generator's known answers, the
-// uniform's bounds, 64-bit egos and seeds, the inverse CDF's edges --, and a shared library whose
-// `os_*` symbols let the CPU tests drive the draws and the two scene functions with a sampler.
-// Never loaded by the belief-planning_amd package.
+// A stand-alone program under the address and undefined-behaviour sanitizers
+// (tests/test_obstacle_sampling.py): the generator's known answers, the uniform's bounds, 64-bit egos
+// and seeds, the inverse CDF's edges.  The CPU tests drive the draws and the scene functions with a
+// sampler through tests/hostsim/scene_host.cpp.  Never loaded by the belief-planning_amd package.
 #include <stdio.h>
 
 #include "bmpc_env_quad.h"
 
 using namespace bmpc;
-
-extern "C" {
-
-void os_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out) { philox4x32_10(counter, key, out); }
-
-// out[i] = obstacle_uniform(seed[i], ego[i], epoch[i])
-void os_uniforms(int n, const uint64_t* seed, const uint64_t* ego, const uint32_t* epoch, double* out) {
-  for (int i = 0; i < n; ++i) out[i] = obstacle_uniform(seed[i], ego[i], epoch[i]);
-}
-
-int os_inverse_cdf(const double* w, int m, double u) { return rng_inverse_cdf(w, m, u); }
-
-// One overtake scene step of `batch` egos as k_env runs it (no statistics).  legacy != 0 calls the
-// scene function with the argument list it had before the sampler (smp is ignored).
-int os_env_step(const bmpc_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch, double* scene,
-                bmpc_policy* pol, const double* upred, int upred_stride, double* x, double* z, double* xref,
-                const bmpc_obstacle_sampling* smp, int legacy) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    if (legacy)
-      env_step_ego(*env, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                   xref + (size_t)e * 4);
-    else
-      env_step_ego(*env, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 4, z + (size_t)e * 4,
-                   xref + (size_t)e * 4, smp, mc, e);
-  }
-  return 0;
-}
-
-// ... and one quadruped scene step, as k_env_quad runs it
-int os_quad_env_step(const bmpc_quad_env_desc* env, const double* mc, double dt, int N, int m, int t, int batch,
-                     double* scene, const bmpc_policy* pol, const double* upred, int upred_stride, double* x,
-                     double* z, double* xref, const bmpc_obstacle_sampling* smp, int legacy) {
-  if (m < 1 || m > BMPC_MAX_M) return -22;
-  for (int e = 0; e < batch; ++e) {
-    double* st = scene + (size_t)e * ENV_STRIDE;
-    const double* u0 = upred ? upred + (size_t)e * upred_stride : nullptr;
-    if (legacy)
-      quad_env_step_ego(*env, mc, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 3, z + (size_t)e * 3,
-                        xref + (size_t)e * 3);
-    else
-      quad_env_step_ego(*env, mc, dt, N, m, t, st, pol + (size_t)e * m, u0, x + (size_t)e * 3, z + (size_t)e * 3,
-                        xref + (size_t)e * 3, smp, e);
-  }
-  return 0;
-}
-
-}  // extern "C"
 
 static int failures = 0;
 #define CHECK(c)                                           \

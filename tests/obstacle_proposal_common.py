@@ -1,39 +1,17 @@
-"""Shared by tests/test_obstacle_proposal.py and tests/test_obstacle_proposal_gpu.py: the host build of
-the weighted obstacle modes (tests/hostsim/obstacle_proposal_host.cpp), teacher-forced host runs of the
-two scenes with a sampler and a proposal, and the NumPy restatement of the two rules -- the choice and
-the log-weight increment of every epoch start from branch probabilities p at the recorded pre-step
-state (bmpc_set_obstacle_proposal; the scenes and the margin rule are obstacle_sampling_common's)."""
+"""Shared by tests/test_obstacle_proposal.py and tests/test_obstacle_proposal_gpu.py: the NumPy
+restatement of the weighted obstacle modes' two rules -- the choice and the log-weight increment of every
+epoch start from branch probabilities p at the recorded pre-step state (bmpc_set_obstacle_proposal; the
+scenes and their host steps are tests/scene_common.py's, the margin rule obstacle_sampling_common's)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import obstacle_sampling_common as S
+import scene_common as SC
 from bmpc import abi, rng
-from common import HERE, PKG, REPO
 
-SRC = os.path.join(HERE, "hostsim", "obstacle_proposal_host.cpp")
-SO = os.path.join(HERE, "hostsim", "libbmpc_hostsim_obstacle_proposal.so")
 LOGW_TOL = 1e-9        # the project's host-versus-NumPy scene bar (tests/test_env_host.py)
 TILTS = {"overtake": (1.0, 4.0, 0.25), "quadruped": (1.0, 5.0)}
-_shim = None
-
-
-def shim():
-    """The shared-library build of the host file, rebuilt when a source it is compiled from is newer."""
-    global _shim
-    if _shim is None:
-        deps = [SRC, os.path.join(REPO, "include", "bmpc.h")] + [
-            os.path.join(PKG, "csrc", f) for f in ("bmpc_rng.h", "bmpc_env_quad.h", "bmpc_env.h", "bmpc_model.h",
-                                                   "bmpc_core.h")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
-            tmp = SO + f".{os.getpid()}.tmp"
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", *S.INCLUDES,
-                                   SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _shim = C.CDLL(SO)
-    return _shim
 
 
 def proposal(sc, tilt=None, script=None, epoch0=0):
@@ -43,44 +21,12 @@ def proposal(sc, tilt=None, script=None, epoch0=0):
     return abi.make_obstacle_proposal(tilt, where, epoch0, m=sc.m), table
 
 
-def host_step(sc, t, scene, pol, u0, smp, prop):
-    """k_env / k_env_quad on the host with a sampler and a proposal: advances `scene` (and the overtake
-    `pol`) in place; x, z, xref."""
-    B, n = scene.shape[0], sc.n
-    x, z, xref = np.zeros((B, n)), np.zeros((B, n)), np.zeros((B, n))
-    up = None if u0 is None else np.ascontiguousarray(np.asarray(u0, float).reshape(B, -1))
-    fn = shim().op_env_step if sc.kind == "overtake" else shim().op_quad_env_step
-    rc = fn(C.byref(sc.env), S._p(sc.mc), C.c_double(sc.desc.dt), sc.desc.N, sc.desc.m, int(t), B, S._p(scene), pol,
-            S._p(up), 0 if up is None else up.shape[1], S._p(x), S._p(z), S._p(xref),
-            None if smp is None else C.byref(smp), None if prop is None else C.byref(prop))
-    assert rc == 0
-    return x, z, xref
-
-
-def host_run(sc, smp, prop, steps, t0=0, egos=None, same_input=False):
-    """`steps` teacher-forced host steps t0 .. t0 + steps - 1 from the scene's initial rows (`egos`: an
-    index array or slice of them; same_input: every ego gets ego 0's scripted input, so that egos
-    from one state differ by the obstacle's choices alone).  Per step: the scene rows after it, the
-    step's x / z outputs -- the choice's pre-step state -- and the policies in force before it."""
-    sel = slice(None) if egos is None else egos
-    scene = np.ascontiguousarray(sc.scene0[sel]).copy()
-    ids = np.arange(sc.B)[sel]
-    pol = abi.policy_array([sc.rows[i] for i in ids])
-    out = []
-    for t in range(t0, t0 + steps):
-        before = S.copy_policies(pol)
-        u0 = None if t == 0 else sc.script(t, np.zeros(len(ids)) if same_input else ids)
-        x, z, _ = host_step(sc, t, scene, pol, u0, smp, prop)
-        out.append(dict(scene=scene.copy(), x=x, z=z, pol=before))
-    return out
-
-
 def host_weights(sc, pol, x, z):
     """The model weights w [B, m] the scene rule forms at (x, z) [B, n] under the policy array `pol`."""
     B = len(x)
     w = np.zeros((B, sc.m))
-    shim().op_weights(0 if sc.kind == "overtake" else 1, S._p(sc.mc), C.c_double(sc.desc.dt), sc.desc.N, sc.m, B, pol,
-                      S._p(np.ascontiguousarray(x)), S._p(np.ascontiguousarray(z)), S._p(w))
+    SC.shim().op_weights(0 if sc.kind == "overtake" else 1, SC._p(sc.mc), C.c_double(sc.desc.dt), sc.desc.N, sc.m, B, pol,
+                      SC._p(np.ascontiguousarray(x)), SC._p(np.ascontiguousarray(z)), SC._p(w))
     return w
 
 

@@ -3,31 +3,22 @@ resampling's rules (tests/hostsim/resample_host.cpp), the weight families of the
 the checks both sides apply to a set of ancestors."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import hostbuild
 from bmpc import resample
-from common import HERE, PKG, REPO
+from common import HERE
 
 SRC = os.path.join(HERE, "hostsim", "resample_host.cpp")
-SO = os.path.join(HERE, "hostsim", "libbmpc_hostsim_resample.so")
-INCLUDES = ["-I" + os.path.join(REPO, "include"), "-I" + os.path.join(PKG, "csrc")]
 _shim = None
 
 
 def shim():
-    """The shared-library build of the host file, rebuilt when a source it is compiled from is newer."""
+    """The shared-library build of the host file (hostbuild.shared), with its prototypes."""
     global _shim
     if _shim is None:
-        deps = [SRC, os.path.join(REPO, "include", "bmpc.h")] + [
-            os.path.join(PKG, "csrc", f) for f in ("bmpc_resample.h", "bmpc_rng.h", "bmpc_core.h")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
-            tmp = SO + f".{os.getpid()}.tmp"
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", *INCLUDES,
-                                   SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _shim = C.CDLL(SO)
+        _shim = hostbuild.shared("resample", [SRC])
         _shim.rs_u53.restype = C.c_uint64
         _shim.rs_u53.argtypes = [C.c_uint64, C.c_int64, C.c_uint32]
         _shim.rs_ess.restype = C.c_double

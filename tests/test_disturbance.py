@@ -1,20 +1,21 @@
 """The actuation disturbance of the device closed loops (bmpc_set_disturbance), host side.
 
 The variate of csrc/bmpc_rng.h as a stand-alone program under the address and undefined-behaviour
-sanitizers (tests/hostsim/disturbance_host.cpp); the same file as a shared library: its draws against
-bmpc/rng.py exactly, the variate's moments, the three scene functions with a disturbance against an
+sanitizers (tests/hostsim/disturbance_host.cpp); the scene steps' host build
+(tests/hostsim/scene_host.cpp) as a shared library: its draws against bmpc/rng.py exactly, the variate's moments, the three scene functions with a disturbance against an
 undisturbed call on NumPy-perturbed inputs bit for bit, and law NONE / sigma 0 against the scene
 functions' former argument list; the ctypes mirror, the argument validation and the population
 entries' plumbing.  The GPU side is tests/test_disturbance_gpu.py."""
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import disturbance_common as D
+import hostbuild
+import scene_common as SC
 from bmpc import abi, plan, rng, scenarios
 from common import REPO
 
@@ -24,13 +25,7 @@ STEPS, B = 8, 65
 def test_host_program_under_sanitizers(tmp_path):
     """Known answers of xi through bmpc_rng.h, its extremes -+ 2 (2^32 - 1) K at the all-zero and
     all-ones output words, counters with g >= 2^32 and seed >= 2^32, and sigma = 0 changing nothing."""
-    exe = tmp_path / "disturbance_host"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover", "-Wall", "-Wno-unknown-pragmas", *D.INCLUDES, D.SRC, "-o", str(exe)]
-    # the sanitizer runtimes linked into the program where the toolchain has them as archives, else the shared ones
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostbuild.sanitized_program("disturbance_host.cpp", tmp_path, flags=["-ffp-contract=off"])
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr[-2000:])
 
 
@@ -66,7 +61,7 @@ def test_draws_equal_numpy_restatement():
     got = np.zeros((n, 8))
     for c in range(8):
         col = np.zeros(n)
-        D.shim().dh_xi(n, D._p(seed), D._p(ego), D._p(step), D._p(np.full(n, 8 + c, np.uint32)), D._p(col))
+        SC.shim().dh_xi(n, SC._p(seed), SC._p(ego), SC._p(step), SC._p(np.full(n, 8 + c, np.uint32)), SC._p(col))
         got[:, c] = col
     np.testing.assert_array_equal(got, want)
     assert len(np.unique(got)) == got.size and np.all(np.abs(got) <= 2 * np.sqrt(3.0))
@@ -99,44 +94,44 @@ def test_moments():
     assert np.abs(corr - np.eye(4)).max() <= 0.016 and np.max(np.abs(lag)) <= 0.016
 
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_host_scene_equals_perturbed_inputs(kind):
     """65 egos, 8 teacher-forced steps: a disturbed call equals an undisturbed call whose u0 and
     obstacle-input slot hold nominal + sigma * bmpc.rng.disturbance(...) formed in NumPy, bit for bit
     in scene, x, z and xref (merge: S and bx too); a shard with ego_base = 40 takes the rows of the
     whole batch; an undisturbed run differs."""
-    sc = D.scene_of(kind, B)
+    sc = SC.Scene(kind, B)
     dist = D.make(kind)
-    got, pol = D.host_run(sc, STEPS, dist=dist)
-    twin, pol_t = D.host_run(sc, STEPS, twin=dist)
+    got, pol = SC.host_run(sc, STEPS, dist=dist)
+    twin, pol_t = SC.host_run(sc, STEPS, twin=D.twin(kind, dist))
     D.assert_same_but_uobs(kind, got, twin)
     assert (pol is None and pol_t is None) or bytes(pol) == bytes(pol_t)
-    plain, _ = D.host_run(sc, STEPS)
+    plain, _ = SC.host_run(sc, STEPS)
     assert not np.array_equal(plain[-1]["x"], got[-1]["x"]) and not np.array_equal(plain[-1]["z"], got[-1]["z"])
     assert np.array_equal(plain[0]["scene"], got[0]["scene"])          # step 0 has no Euler step
-    part, _ = D.host_run(sc, STEPS, dist=D.make(kind, ego_base=40), egos=slice(40, 60))
+    part, _ = SC.host_run(sc, STEPS, dist=D.make(kind, ego_base=40), egos=slice(40, 60))
     for a, b in zip(got, part):
-        for k in b:
+        for k in set(b) - {"pol"}:
             assert np.array_equal(a[k][40:60], b[k]), k
     # one channel at a time: sigma_ego alone leaves the obstacle alone, and the other way round
     zero = (0.0,) * D.slot(kind)[1]
-    ego_only, _ = D.host_run(sc, STEPS, dist=D.make(kind, sigma_obs=zero))
-    obs_only, _ = D.host_run(sc, STEPS, dist=D.make(kind, sigma_ego=zero))
+    ego_only, _ = SC.host_run(sc, STEPS, dist=D.make(kind, sigma_obs=zero))
+    obs_only, _ = SC.host_run(sc, STEPS, dist=D.make(kind, sigma_ego=zero))
     if kind == "merge":   # (the other scenes' obstacles react to the ego)
         assert np.array_equal(ego_only[-1]["z"], plain[-1]["z"]) and np.array_equal(obs_only[-1]["x"], plain[-1]["x"])
     assert not np.array_equal(ego_only[-1]["x"], plain[-1]["x"]) and not np.array_equal(obs_only[-1]["z"], plain[-1]["z"])
 
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_off_is_the_former_function(kind):
     """Law NONE with non-zero sigmas, law IH4 with all sigmas zero and no disturbance at all reproduce
     the scene function's former argument list bit for bit over the same 8 steps."""
-    sc = D.scene_of(kind, B)
-    ref, ref_pol = D.host_run(sc, STEPS, legacy=True)
+    sc = SC.Scene(kind, B)
+    ref, ref_pol = SC.host_run(sc, STEPS, arglist=1)
     zero = (0.0,) * D.slot(kind)[1]
     for dist in (D.make(kind, law=abi.DISTURB_NONE, seed=2 ** 63 + 99, ego_base=12),
                  D.make(kind, sigma_ego=zero, sigma_obs=zero), None):
-        got, got_pol = D.host_run(sc, STEPS, dist=dist)
+        got, got_pol = SC.host_run(sc, STEPS, dist=dist)
         D.assert_same_but_uobs(kind, ref, got)
         assert (ref_pol is None and got_pol is None) or bytes(ref_pol) == bytes(got_pol)
 
@@ -151,18 +146,11 @@ def test_disturbance_layout_matches_header(tmp_path):
     code = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmpc.h"\n'
             'int main(){printf("' + "%zu " * (1 + len(FIELDS)) + '%d %d %d\\n", sizeof(bmpc_disturbance), ' + offs
             + ', (int)BMPC_DISTURB_NONE, (int)BMPC_DISTURB_IH4, (int)BMPC_MAX_D);return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o",
-                           str(tmp_path / "t")])
-    got = list(map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split()))
+    got = hostbuild.header_program(tmp_path, code, cxx=True)   # (C++: the header's own static_assert)
     S = abi.Disturbance
     assert [name for name, _ in S._fields_] == list(FIELDS)
     assert got == [C.sizeof(S)] + [getattr(S, f).offset for f in FIELDS] + [abi.DISTURB_NONE, abi.DISTURB_IH4, abi.MAX_D]
     assert got[:7] == [88, 0, 4, 8, 16, 24, 56]
-    # the header's own static_assert holds where it is compiled as C++
-    (tmp_path / "t.cpp").write_text('#include "bmpc.h"\nint main(){return 0;}\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                           str(tmp_path / "t.cpp")])
     assert "static_assert(sizeof(bmpc_disturbance) ==" in open(os.path.join(REPO, "include", "bmpc.h")).read()
 
 
@@ -227,8 +215,9 @@ def test_population_entries_plumb_the_disturbance():
             (None, None, 0, None, 1, 0)
     assert list(inspect.signature(scenarios.disturbed_merge_population).parameters) == common + ["ego_base", "population"]
     assert list(inspect.signature(scenarios.merge_population).parameters) == ["B", "steps", "seed", "device", "record"]
-    assert list(inspect.signature(scenarios._merge_loop).parameters) == list(
-        inspect.signature(scenarios._overtake_loop).parameters)
+    # one driver takes every scene's plan: no scene has a loop of its own with its own parameter list
+    assert list(inspect.signature(scenarios._closed_loop).parameters)[:5] == ["pl", "scene0", "steps", "record", "device"]
+    assert not [n for n in vars(scenarios) if n.endswith("_loop") and n != "_closed_loop"]
 
     class Plan:
         def set_disturbance(self, sigma_ego, sigma_obs, seed, ego_base):

@@ -9,20 +9,20 @@ only if the device applies exactly NumPy's numbers.
 
 Every case asserts that all its solves succeeded (CVaR: 0 or 10, OSQP-class: 1) with the issue's
 suggested sigmas, highway (0.3, 0.01) / (0.5, 0.02), quadruped (0.02, 0.01, 0.05) for both vehicles.
-The scenes, plans and helpers are those of tests/test_loop_record_gpu.py; 6 steps everywhere."""
+The scenes, plans and helpers are those of tests/loop_common.py; 6 steps everywhere."""
 import numpy as np
 import pytest
 
 import disturbance_common as D
+import scene_common as SC
 from bmpc import abi
 from bmpc.scenarios import highway_desc, merge_desc, quadruped_desc
-from test_loop_record_gpu import (COLUMNS, Loop, assert_record_equals, assert_same_finals, gpu, merge_case,  # noqa: F401
-                                  overtake_case, quad_case, set_path)
+from loop_common import (BLK, COLUMNS, Loop, assert_record_equals, assert_same_finals, gpu, merge_case,  # noqa: F401
+                         overtake_case, quad_case, recorded, set_path)
 
 pytestmark = pytest.mark.gpu
 
 STEPS = 6
-BLK = (abi.KERNEL_IPM_BLK4, abi.KERNEL_IPM_BLK8)
 # name: (scene, egos, BMPC_BLOCK_EGOS, BMPC_LDS_RICH, the per-step solver kernels, the loop's kernels)
 PATHS = {
     "overtake_wave": ("overtake", 65, 0, 1, (abi.KERNEL_IPM_RICH,), (abi.KERNEL_LOOP_RICH,)),
@@ -68,7 +68,7 @@ def perturb_on_device(d, dist):
 
 
 def manual(plan, case, dist=None, twin=None, tilt=None, steps=STEPS):
-    """test_loop_record_gpu.manual with a disturbance attached (`dist`) or applied from outside to an
+    """loop_common.manual with a disturbance attached (`dist`) or applied from outside to an
     undisturbed plan (`twin`): the columns a record must hold, the kernels taken, the final state."""
     d = attach(Loop(plan, case), dist, tilt)
     rows = {k: [] for k in COLUMNS}
@@ -88,17 +88,11 @@ def manual(plan, case, dist=None, twin=None, tilt=None, steps=STEPS):
 
 def looped(plan, case, chunks, dist=None, tilt=None, detach=False):
     """The loop in `chunks` calls with a recorder: the record, the kernels reported, the final state."""
-    d = attach(Loop(plan, case), dist, tilt)
-    if detach:
-        d.pl.set_disturbance(None)
-    rec = d.pl.new_loop_record(sum(chunks), 0, predictions=True)
-    d.pl.set_loop_record(rec)
-    kernels = []
-    for c in chunks:
-        d.loop(c)
-        d.stream.synchronize()
-        kernels.append(d.pl.last_kernel())
-    return rec.host(), kernels, d.finals()
+    def setup(d):
+        attach(d, dist, tilt)
+        if detach:
+            d.pl.set_disturbance(None)
+    return recorded(plan, case, chunks, setup=setup)
 
 
 def assert_all_solved(case, cols):
@@ -134,14 +128,14 @@ def reference(plan, monkeypatch, name):
 
 # ---- 1: the scene kernels ----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_scene_kernels_equal_perturbed_inputs(gpu, kind):
     """k_env / k_env_merge / k_env_quad teacher-forced over 6 steps at 65 egos: the disturbed plan
     equals an undisturbed plan whose upred[:, 0] and obstacle-input slots are perturbed with NumPy's
     numbers before each step, bit for bit (merge: the transform slots too)."""
     import torch
     case, dist = case_of(kind, 65), D.make(kind)
-    script = D.scene_of(kind, 65).script
+    script = SC.Scene(kind, 65).script
     a, b, c = attach(Loop(gpu, case), dist), Loop(gpu, case), Loop(gpu, case)
     moved = False
     for t in range(STEPS):
@@ -222,7 +216,7 @@ def test_tilted_sampler_rides_along(gpu, monkeypatch):
 
 # ---- 3: off is the parent ----------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_off_computes_the_undisturbed_bits(gpu, monkeypatch, kind):
     """Sigma = 0, law NONE with non-zero sigmas, and attach-then-detach (with and, on the overtake
     scene, beside an unused proposal that keeps the options block alive) give the bits of a plan that
@@ -272,7 +266,7 @@ def test_merge_channels_are_separate(gpu, monkeypatch):
 
 # ---- 5, 6: shards and seeds ---------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_shard_and_seed(gpu, monkeypatch, kind):
     """Egos 40..59 in a plan of their own with ego_base = 40 take the rows they have in the 65-ego run;
     with ego_base = 0 they do not.  The same seed twice is identical (the launch-path test ran it
@@ -297,7 +291,7 @@ def test_shard_and_seed(gpu, monkeypatch, kind):
 
 # ---- 7: clones ----------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("kind", D.KINDS)
+@pytest.mark.parametrize("kind", SC.KINDS)
 def test_clones_diverge_by_themselves(gpu, monkeypatch, kind):
     """3 steps, then every ego becomes a copy of ego 0 (gather_egos with a broadcast), then 2 more
     steps: with sigma > 0 the clones leave their ancestor -- a draw is addressed by slot --, with

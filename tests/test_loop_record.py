@@ -5,14 +5,12 @@ of plan.LoopRecording on synthetic arrays, and the *_population signatures.  The
 tests/test_loop_record_gpu.py."""
 import ctypes as C
 import inspect
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 from bmpc import abi, plan, scenarios
-from common import HERE, PKG, REPO
 
 FIELDS = ("capacity", "t_base", "scene", "xref", "u", "J", "status", "iters", "upred", "xpred", "zpred", "branch_w")
 
@@ -22,9 +20,7 @@ def test_loop_record_layout_matches_header(tmp_path):
     code = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmpc.h"\n'
             'int main(){printf("' + "%zu " * (1 + len(FIELDS)) + '\\n", sizeof(bmpc_loop_record), ' + offs
             + ');return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
-    got = list(map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split()))
+    got = hostbuild.header_program(tmp_path, code)
     D = abi.LoopRecord
     assert [name for name, _ in D._fields_] == list(FIELDS)
     assert got == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS]
@@ -34,15 +30,7 @@ def test_row_writer_host_program_under_sanitizers(tmp_path):
     """B = 3, capacity 3 from step 1, steps 0..4 over a fake slab: rows hold steps 1..3, steps 0 and 4
     write nothing, every guard margin keeps its sentinel, NULL optional columns are skipped, and the
     offset of ego 65,535's last row at capacity 4,096 and width 1,480 (beyond 2^32) is exact."""
-    exe = tmp_path / "loop_record_host"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-Wall",
-           "-Wno-unknown-pragmas", "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(PKG, "csrc"),
-           os.path.join(HERE, "hostsim", "loop_record_host.cpp"), "-o", str(exe)]
-    # the sanitizer runtimes linked into the program where the toolchain has them as archives (the
-    # program then needs nothing of its environment's library order), else the shared ones
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostbuild.sanitized_program("loop_record_host.cpp", tmp_path)
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr[-2000:])
 
 

@@ -16,148 +16,11 @@ import numpy as np
 import pytest
 
 from bmpc import abi
-from bmpc.scenarios import (highway_desc, highway_policy_rows, merge_desc, merge_lane_ref, merge_policy_rows,
-                            quad_scene, quadruped_policy_rows, seeded_batch, seeded_merge_batch)
-from common import golden
+from bmpc.scenarios import highway_desc
+from loop_common import (BLK, Loop, assert_record_equals, assert_same_finals, gpu, manual, merge_case,  # noqa: F401
+                         overtake_case, quad_case, recorded, set_path)
 
 pytestmark = pytest.mark.gpu
-
-COLUMNS = ("scene", "xref", "u", "J", "status", "iters", "upred", "xpred", "zpred", "branch_w")
-FINALS = ("scene", "up", "J", "st", "it", "stats", "x", "z", "xref")
-BLK = (abi.KERNEL_IPM_BLK4, abi.KERNEL_IPM_BLK8)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no HIP device")
-    from bmpc import plan
-    plan.context(0)
-    return plan
-
-
-def set_path(monkeypatch, block_egos=None, rich=None, fused=None):
-    """The launch path of the plans made next (read from the environment on every launch)."""
-    for k, v in (("BMPC_BLOCK_EGOS", block_egos), ("BMPC_LDS_RICH", rich), ("BMPC_LOOP_FUSED", fused),
-                 ("BMPC_BLOCK_WAVES", None)):
-        monkeypatch.delenv(k, raising=False)
-        if v is not None:
-            monkeypatch.setenv(k, str(v))
-
-
-# ---- the scenes ----------------------------------------------------------------------------------
-
-def overtake_case(N, NB, B, robust=False):
-    x, z, _, tgt = (a[:B] for a in seeded_batch(300, seed=5))
-    desc = highway_desc(N=N, NB=NB)
-    if robust:
-        desc.controller = abi.CTRL_ROBUST
-    scene = np.zeros((B, abi.ENV_STRIDE))
-    scene[:, abi.ENV_X:abi.ENV_X + 4], scene[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
-    return dict(kind="overtake", desc=desc, scene=scene, policies=highway_policy_rows(tgt), env=abi.make_env())
-
-
-def merge_case(B):
-    x, z = seeded_merge_batch(B)
-    scene = np.zeros((B, abi.ENV_STRIDE))
-    scene[:, abi.ENV_X:abi.ENV_X + 4], scene[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
-    return dict(kind="merge", desc=merge_desc(N=12), scene=scene, policies=merge_policy_rows(B), env=None)
-
-
-def quad_case(B):
-    from test_quad_loop import NAME, fixture_desc, loop_batch, scene_env
-    g = golden(NAME)
-    x, z, x_des = (a[:B] for a in loop_batch(300))
-    return dict(kind="quadruped", desc=fixture_desc(g, 6), scene=quad_scene(x, z, x_des),
-                policies=quadruped_policy_rows(B, float(g["v0"])), env=scene_env(g))
-
-
-class Loop:
-    """A plan of one of the scenes with the device buffers of its closed loop."""
-
-    def __init__(self, plan, case):
-        import torch
-        self.torch, self.kind, self.env = torch, case["kind"], case["env"]
-        B = self.B = len(case["scene"])
-        self.pl = pl = plan.BatchPlan(case["desc"], B)
-        pl.set_policies(case["policies"])
-        if self.kind == "merge":
-            pl.set_merge_scene(abi.make_merge_env(), *merge_lane_ref())
-        n, d = pl.desc.n, pl.desc.d
-        dev = torch.device("cuda", 0)
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.scene = torch.tensor(case["scene"], **f64)
-        self.up = torch.zeros((B, pl.U, d), **f64)
-        self.J = torch.zeros(B, **f64)
-        self.st = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.it = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.stats = torch.zeros((B, abi.ENV_NSTAT), **f64)
-        self.x, self.z, self.xref = (torch.zeros((B, n), **f64) for _ in range(3))
-        self.xpred = torch.zeros((B, pl.T, n), **f64)
-        self.bw = torch.zeros((B, max(pl.nbranch - 1, 1)), **f64)
-        torch.cuda.synchronize()
-        self.stream = torch.cuda.Stream(dev)
-        self.t = 0
-
-    def _ptrs(self, *names):
-        return [getattr(self, n).data_ptr() for n in names]
-
-    def env_step(self):
-        args = self._ptrs("scene", "up", "x", "z", "xref", "J", "st", "it", "stats")
-        s = self.stream.cuda_stream
-        if self.kind == "overtake":
-            self.pl.env_step_device(self.env, self.t, *args, stream=s)
-        elif self.kind == "merge":
-            self.pl.merge_env_step_device(self.t, *args, stream=s)
-        else:
-            self.pl.quad_env_step_device(self.env, self.t, *args, stream=s)
-        self.t += 1
-
-    def solve(self):
-        self.pl.solve_device(*self._ptrs("x", "z", "xref", "up", "xpred", "bw", "J", "st", "it"), self.stream.cuda_stream)
-
-    def loop(self, n):
-        args = self._ptrs("scene", "up", "x", "z", "xref", "J", "st", "it", "stats")
-        s = self.stream.cuda_stream
-        if self.kind == "overtake":
-            self.pl.loop_device(self.env, self.t, n, *args, s)
-        elif self.kind == "merge":
-            self.pl.merge_loop_device(self.t, n, *args, s)
-        else:
-            self.pl.quad_loop_device(self.env, self.t, n, *args, s)
-        self.t += n
-
-    def host(self, *names):
-        self.stream.synchronize()
-        return [getattr(self, n).cpu().numpy().copy() for n in names]
-
-    def finals(self):
-        out = dict(zip(FINALS, self.host(*FINALS)))
-        if self.pl.desc.controller == abi.CTRL_ROBUST:
-            out["ws"] = self.pl.get_robust_warm_start()
-        else:
-            out["ws"] = self.pl.get_warm_start()
-        return out
-
-
-def manual(plan, case, steps):
-    """`steps` closed-loop steps as their launches with a host copy after each: the columns a record of
-    the same loop must hold [B, steps, ...], the kernels taken and the loop's final state."""
-    d = Loop(plan, case)
-    robust = d.pl.desc.controller == abi.CTRL_ROBUST
-    rows = {k: [] for k in COLUMNS}
-    kernels = set()
-    for _ in range(steps):
-        d.env_step()
-        d.solve()
-        scene, xref, up, J, st, it, xpred, bw = d.host("scene", "xref", "up", "J", "st", "it", "xpred", "bw")
-        kernels.add(d.pl.last_kernel())
-        for k, v in zip(COLUMNS, (scene, xref, up[:, 0], J, st, it, up, xpred,
-                                  None if robust else d.pl.tree()["zbar"], bw[:, :d.pl.nbranch - 1])):
-            rows[k].append(v)
-    cols = {k: np.stack(v, axis=1) for k, v in rows.items() if v[0] is not None}
-    return cols, kernels, d.finals()
 
 
 def assert_solved(case, ref):
@@ -171,41 +34,6 @@ def assert_solved(case, ref):
         assert np.all(st == 1), np.argwhere(st != 1)
     assert np.all(np.isfinite(ref["J"])) and np.all(np.isfinite(ref["xpred"]))
     assert np.array_equal(ref["scene"][:, :, abi.ENV_STEPS], np.tile(np.arange(1, st.shape[1] + 1.0), (st.shape[0], 1)))
-
-
-def recorded(plan, case, chunks, predictions=True, attach=True):
-    """The loop in `chunks` calls with one recorder attached throughout: the record on the host, the
-    kernel reported after each call and the loop's final state."""
-    d = Loop(plan, case)
-    rec = None
-    if attach:
-        rec = d.pl.new_loop_record(sum(chunks), 0, predictions=predictions)
-        d.pl.set_loop_record(rec)
-    kernels = []
-    for c in chunks:
-        d.loop(c)
-        d.stream.synchronize()
-        kernels.append(d.pl.last_kernel())
-    out = d.finals()
-    return (None if rec is None else rec.host()), kernels, out
-
-
-def assert_record_equals(rec, ref, rows=None):
-    names = [k for k in COLUMNS if k in ref]
-    assert sorted(rec.cols) == sorted(names)
-    for k in names:
-        want = ref[k] if rows is None else ref[k][:, rows]
-        assert rec.col(k).shape == want.shape and rec.col(k).dtype == want.dtype, k
-        assert np.array_equal(rec.col(k), want), (k, np.argwhere(rec.col(k) != want)[:4])
-
-
-def assert_same_finals(a, b):
-    for k in a:
-        if k == "ws":
-            for kk in a[k]:
-                assert np.array_equal(a[k][kk], b[k][kk]), ("warm start", kk)
-        else:
-            assert np.array_equal(a[k], b[k]), k
 
 
 _REF = {}

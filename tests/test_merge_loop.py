@@ -5,7 +5,7 @@ The recording is exactly self-consistent with the scene's rules (Highway_env_bra
 traj_x[t+1] from traj_x[t] and traj_u[t], traj_z from traj_obs_u, traj_obs_u from the main-road
 backup 0, traj_S / traj_xRef / traj_bx from refX / refY / refpsi.  The ego leaves the ramp at step 19.
 
-Host build (not gpu): the scene function itself, compiled with g++ (tests/hostsim/merge_env_host.cpp),
+Host build (not gpu): the scene function itself, compiled with g++ (tests/hostsim/scene_host.cpp),
 driven through all 60 recorded steps with the recorded inputs; bar 1e-9 as tests/test_env_host.py
 (tan / cos / sin of a different libm), the obstacle's input 1e-12.
 
@@ -15,41 +15,19 @@ k_loop against the per-step launches bit for bit, LDS-rich and lean; a free run 
 the refusals.
 """
 import ctypes as C
-import os
-import subprocess
+import types
 
 import numpy as np
 import pytest
 
+import hostbuild
+import scene_common as SC
 from bmpc import abi
+from bmpc.scenarios import _overtake_scene as new_scene
 from bmpc.scenarios import merge_desc, merge_lane_ref, merge_policy_rows
-from common import HERE, PKG, REPO, golden
+from common import golden
 from test_merge import NAME, check_merge_replay, replay_inputs
 from test_merge import merge_desc as golden_merge_desc
-
-SRC = os.path.join(HERE, "hostsim", "merge_env_host.cpp")
-SO = os.path.join(HERE, "hostsim", "libbmpc_hostsim_merge_env.so")
-_shim = None
-
-
-def shim():
-    """The host build of the scene function, rebuilt when a source it is compiled from is newer."""
-    global _shim
-    if _shim is None:
-        deps = [SRC, os.path.join(REPO, "include", "bmpc.h")] + [
-            os.path.join(PKG, "csrc", f) for f in ("bmpc_env_merge.h", "bmpc_env.h", "bmpc_model.h", "bmpc_core.h")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
-            tmp = SO + f".{os.getpid()}.tmp"
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas",
-                                   "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(PKG, "csrc"), SRC,
-                                   "-o", tmp])
-            os.replace(tmp, SO)
-        _shim = C.CDLL(SO)
-    return _shim
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def scene_env(g):
@@ -59,25 +37,10 @@ def scene_env(g):
 
 def host_env_step(g, t, scene, upred=None, J=None, status=None, iters=None, stats=None, dt=0.1):
     """k_env_merge on the host: advances `scene` [B][16] in place; returns x, z, xref, S, bx."""
-    B = scene.shape[0]
     ref = np.ascontiguousarray(np.concatenate([g["refX"], g["refY"], g["refpsi"]]).astype(float))
-    bxp = np.ascontiguousarray(np.asarray(g["bx"], float))
-    x, z, xref, S, bx = np.zeros((B, 4)), np.zeros((B, 4)), np.zeros((B, 4)), np.zeros((B, 4, 4)), np.zeros((B, 4))
-    up = None if upred is None else np.ascontiguousarray(np.asarray(upred, float).reshape(B, -1))
-    env = scene_env(g)
-    rc = shim().ms_env_step(C.byref(env), len(g["refX"]), _p(ref), _p(bxp), 4, C.c_double(dt), int(t), B, _p(scene),
-                            _p(up), 0 if up is None else up.shape[1], _p(J), _p(status), _p(iters), _p(x), _p(z),
-                            _p(xref), _p(S), _p(bx), _p(stats))
-    assert rc == 0
-    return x, z, xref, S, bx
-
-
-def new_scene(x, z):
-    x = np.atleast_2d(np.asarray(x, float))
-    scene = np.zeros((x.shape[0], abi.ENV_STRIDE))
-    scene[:, abi.ENV_X:abi.ENV_X + 4] = x
-    scene[:, abi.ENV_Z:abi.ENV_Z + 4] = np.atleast_2d(np.asarray(z, float))
-    return scene
+    sc = types.SimpleNamespace(kind="merge", n=4, env=scene_env(g), desc=types.SimpleNamespace(dt=dt), ref=ref,
+                               bx=np.ascontiguousarray(np.asarray(g["bx"], float)))
+    return SC.host_step(sc, t, scene, None, upred, solve=(J, status, iters, stats))
 
 
 def check_scene_step(g, t, scene, x, z, xref, S, bx):
@@ -106,9 +69,7 @@ def test_merge_env_desc_layout_matches_header(tmp_path):
     code = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmpc.h"\n'
             'int main(){printf("%zu %zu %zu %zu\\n", sizeof(bmpc_merge_env_desc), offsetof(bmpc_merge_env_desc, merge_s),'
             ' offsetof(bmpc_merge_env_desc, psimax), offsetof(bmpc_merge_env_desc, vwid));return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
-    size, a, b, c = map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split())
+    size, a, b, c = hostbuild.header_program(tmp_path, code)
     D = abi.MergeEnvDesc
     assert (size, a, b, c) == (C.sizeof(D), D.merge_s.offset, D.psimax.offset, D.vwid.offset)
 

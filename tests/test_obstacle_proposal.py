@@ -1,21 +1,21 @@
 """The weighted obstacle modes of the device closed loops (bmpc_set_obstacle_proposal), host side.
 
 The tilted and the scripted rule of csrc/bmpc_env.h as a stand-alone program under the address and
-undefined-behaviour sanitizers (tests/hostsim/obstacle_proposal_host.cpp); the same file as a shared
-library: a tilt of ones against mode 1 bit for bit, tilted and scripted choices and log-weights against
+undefined-behaviour sanitizers (tests/hostsim/obstacle_proposal_host.cpp); the scene steps' host build
+(tests/hostsim/scene_host.cpp) as a shared library: a tilt of ones against mode 1 bit for bit, tilted and scripted choices and log-weights against
 NumPy over oracle.model's branch_eval, a full enumeration's probabilities summing to one, the
 likelihood ratio's mean, bmpc.montecarlo, the ctypes mirror, the argument validation and the population
 entries' plumbing.  The GPU side is tests/test_obstacle_proposal_gpu.py."""
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import obstacle_proposal_common as P
-import obstacle_sampling_common as S
+import scene_common as SC
 from bmpc import abi, montecarlo, plan, scenarios
 from common import REPO
 
@@ -36,13 +36,7 @@ def test_host_program_under_sanitizers(tmp_path):
     """A tilt of ones against mode 1, the log-weight of a tilted and of a scripted choice, the script's
     clamps at a heap table of exactly its size, the epochs' untouched steps and whole scene steps of
     both scenes in both modes, compiled with -fsanitize=address,undefined and run once."""
-    exe = tmp_path / "obstacle_proposal_host"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-Wall",
-           "-Wno-unknown-pragmas", *S.INCLUDES, P.SRC, "-o", str(exe)]
-    # the sanitizer runtimes linked into the program where the toolchain has them as archives, else the shared ones
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostbuild.sanitized_program("obstacle_proposal_host.cpp", tmp_path)
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr[-2000:])
 
 
@@ -57,19 +51,13 @@ def test_obstacle_proposal_layout_matches_header(tmp_path):
             'int main(){printf("' + "%zu " * (1 + len(FIELDS)) + '%d %d %d %d\\n", sizeof(bmpc_obstacle_proposal), '
             + offs + ', (int)BMPC_ENV_LOGW, (int)BMPC_OBS_SAMPLE_TILTED, (int)BMPC_OBS_SCRIPT, (int)BMPC_ENV_STRIDE);'
             'return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o",
-                           str(tmp_path / "t")])
-    got = list(map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split()))
+    got = hostbuild.header_program(tmp_path, code, cxx=True)
     D = abi.ObstacleProposal
     assert [name for name, _ in D._fields_] == list(FIELDS)
     assert got == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS] + [abi.ENV_LOGW, abi.OBS_SAMPLE_TILTED,
                                                                            abi.OBS_SCRIPT, abi.ENV_STRIDE]
     assert got == [48, 0, 32, 40, 44, 15, 2, 3, 16]
-    # the header's own static_asserts (this struct's and the sampler's, still 24 bytes) hold as C++
-    (tmp_path / "t.cpp").write_text('#include "bmpc.h"\nint main(){return 0;}\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                           str(tmp_path / "t.cpp")])
+    # (cxx: the header's own static_asserts -- this struct's and the sampler's, still 24 bytes -- hold as C++)
     header = open(os.path.join(REPO, "include", "bmpc.h")).read()
     assert "static_assert(sizeof(bmpc_obstacle_proposal) ==" in header
     assert "static_assert(sizeof(bmpc_obstacle_sampling) == 24" in header and C.sizeof(abi.ObstacleSampling) == 24
@@ -82,10 +70,10 @@ def test_obstacle_proposal_layout_matches_header(tmp_path):
 def test_tilt_of_ones_is_mode_model(kind, hold):
     """64 egos, 8 teacher-forced steps: mode 2 with b == 1 gives mode 1's scene rows, outputs and
     policies bit for bit, and ENV_LOGW is exactly 0.0 in every row."""
-    sc = S.Scene(kind, 64)
-    ref = P.host_run(sc, sampling("model", hold), None, 8)
+    sc = SC.Scene(kind, 64)
+    ref = SC.host_run(sc, 8, sampling("model", hold), None)[0]
     prop, _ = P.proposal(sc, np.ones(sc.m))
-    got = P.host_run(sc, sampling("tilted", hold), prop, 8)
+    got = SC.host_run(sc, 8, sampling("tilted", hold), prop)[0]
     for a, b in zip(ref, got):
         for k in ("scene", "x", "z"):
             assert a[k].tobytes() == b[k].tobytes(), k
@@ -93,7 +81,7 @@ def test_tilt_of_ones_is_mode_model(kind, hold):
         assert np.all(b["scene"][:, abi.ENV_LOGW] == 0.0) and not np.signbit(b["scene"][:, abi.ENV_LOGW]).any()
     # ... and another tilt gives other choices somewhere
     prop, _ = P.proposal(sc, P.TILTS[kind])
-    other = P.host_run(sc, sampling("tilted", hold), prop, 8)
+    other = SC.host_run(sc, 8, sampling("tilted", hold), prop)[0]
     assert (stack(other)[:, :, abi.ENV_OBSPOL] != stack(ref)[:, :, abi.ENV_OBSPOL]).any()
 
 
@@ -107,10 +95,10 @@ def test_tilted_choices_and_weights(kind, hold):
     running sum of log(p_j / q_j) within 1e-9.  Decisions within 1e-9 of a partial sum are left out, at
     most 1 % of them; with seed 7 the NumPy side alone leaves out none (asserted here), so every decision
     is compared."""
-    sc = S.Scene(kind, 64)
+    sc = SC.Scene(kind, 64)
     smp = sampling("tilted", hold)
     prop, _ = P.proposal(sc, P.TILTS[kind])
-    run = P.host_run(sc, smp, prop, 8)
+    run = SC.host_run(sc, 8, smp, prop)[0]
     p_at = P.oracle_probabilities(sc, run)
     cache = {}
     p_once = lambda r: cache[r] if r in cache else cache.setdefault(r, p_at(r))   # noqa: E731
@@ -130,18 +118,18 @@ def test_script_is_followed(kind):
     outside [0, m) clamped, ENV_LOGW the NumPy sum of log p_j (oracle.model) within 1e-9 on top of the
     row's starting value, the second step of every epoch leaving choice and weight alone; the seed
     changes nothing."""
-    sc = S.Scene(kind, 64)
+    sc = SC.Scene(kind, 64)
     g = np.random.default_rng(11)
     script = g.integers(0, sc.m, (64, 4))
     script[g.integers(0, 64, 12), g.integers(0, 4, 12)] = g.choice([-3, -1, sc.m, sc.m + 5], 12)
     assert (script < 0).any() and (script >= sc.m).any()
     prop, table = P.proposal(sc, None, script, epoch0=3)
     sc.scene0[:, abi.ENV_LOGW] = -0.5          # (accumulates onto what the row holds)
-    run = P.host_run(sc, sampling("script", 2), prop, 8, t0=6)
+    run = SC.host_run(sc, 8, sampling("script", 2), prop, t0=6)[0]
     _, logw = P.check_weighted(sampling("script", 2), sc.m, stack(run), P.oracle_probabilities(sc, run), script=script,
                                epoch0=3, t0=6, logw0=-0.5)
     assert np.all(logw < -0.5)
-    again = P.host_run(sc, sampling("script", 2, seed=12345), prop, 8, t0=6)
+    again = SC.host_run(sc, 8, sampling("script", 2, seed=12345), prop, t0=6)[0]
     assert stack(again).tobytes() == stack(run).tobytes()
 
 
@@ -157,12 +145,12 @@ def test_enumeration_sums_to_one(kind, epochs, hold):
     paths = montecarlo.enumerate_scripts(m, epochs)
     n = len(paths)
     assert n == (81 if kind == "overtake" else 32)
-    sc = S.Scene(kind, n)
+    sc = SC.Scene(kind, n)
     sc.scene0[:] = sc.scene0[0]
     sc.rows = [sc.rows[0]] * n
     steps = epochs * hold
     prop, table = P.proposal(sc, None, paths)
-    run = P.host_run(sc, sampling("script", hold), prop, steps, same_input=True)
+    run = SC.host_run(sc, steps, sampling("script", hold), prop, same_input=True)[0]
     logp = run[-1]["scene"][:, abi.ENV_LOGW]
     total = np.exp(logp).sum()
     print(kind, "sum of path probabilities - 1 =", total - 1.0)
@@ -172,11 +160,11 @@ def test_enumeration_sums_to_one(kind, epochs, hold):
     # the tilted population from the same state
     b = np.array(P.TILTS[kind])
     B = 256
-    pop = S.Scene(kind, B)
+    pop = SC.Scene(kind, B)
     pop.scene0[:] = pop.scene0[0]
     pop.rows = [pop.rows[0]] * B
     tprop, _ = P.proposal(pop, b)
-    trun = P.host_run(pop, sampling("tilted", hold), tprop, steps, same_input=True)
+    trun = SC.host_run(pop, steps, sampling("tilted", hold), tprop, same_input=True)[0]
     chosen = stack(trun)[:, ::hold, abi.ENV_OBSPOL].astype(int)
     index = (chosen * m ** np.arange(epochs - 1, -1, -1)).sum(1)
     assert np.array_equal(paths[index], chosen) and len(np.unique(index)) >= 8
@@ -198,18 +186,18 @@ def test_likelihood_ratio_is_unbiased(kind):
     and weights from the recorded model weights and bmpc.rng -- reproduces ENV_LOGW within 1e-9 and
     passes the same two bounds."""
     B = 4096
-    sc = S.Scene(kind, B)
+    sc = SC.Scene(kind, B)
     b = np.array(P.TILTS[kind])
     smp = sampling("tilted")
     prop, _ = P.proposal(sc, b)
-    run = P.host_run(sc, smp, prop, 4)
+    run = SC.host_run(sc, 4, smp, prop)[0]
 
     def p_at(r):
         w = P.host_weights(sc, run[r]["pol"], run[r]["x"], run[r]["z"])
         return w / w.sum(1, keepdims=True)
 
     _, numpy_logw = P.check_weighted(smp, sc.m, stack(run), p_at, tilt=b)
-    plain = P.host_run(sc, sampling("model"), None, 1)
+    plain = SC.host_run(sc, 1, sampling("model"), None)[0]
     hit_plain = plain[0]["scene"][:, abi.ENV_OBSPOL] == 1
     freq = hit_plain.mean()
     band = 5.0 * np.sqrt(freq * (1.0 - freq) / B)

@@ -2,7 +2,7 @@
 
 Shapes: overtake N = 6, NB = 1, m = 3 at 27 egos -- the full enumeration of 3 epochs of 2 steps from one
 state, 6 steps -- and quadruped N = 6, NB = 2, m = 2 at 16 egos -- 4 epochs of 2 steps, 8 steps; the
-launch paths are selected as tests/test_loop_record_gpu.py does (BMPC_BLOCK_EGOS=0 / BMPC_LDS_RICH for
+launch paths are selected as tests/loop_common.py does (BMPC_BLOCK_EGOS=0 / BMPC_LDS_RICH for
 the one-wave kernels and the fused k_loop, the defaults for the small-batch kernel).  The state is row 0
 of the batches whose loops the existing GPU tests hold to solving; every case asserts the kernel the
 plan reports and that every solve succeeded.
@@ -15,11 +15,11 @@ import numpy as np
 import pytest
 
 import obstacle_proposal_common as P
-import obstacle_sampling_common as S
+import scene_common as SC
 from bmpc import abi, montecarlo
 from bmpc.scenarios import highway_desc, merge_desc, quadruped_desc
-from test_loop_record_gpu import BLK, Loop, assert_same_finals, gpu, overtake_case, quad_case, set_path  # noqa: F401
-from test_obstacle_sampling_gpu import PATHS, assert_all_solved, model_p
+from loop_common import (PATHS, Loop, assert_all_solved, assert_same_finals, gpu, manual, model_p,  # noqa: F401
+                         overtake_case, quad_case, recorded, set_path)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,35 +47,16 @@ def attach(pl, kind, mode, paths, hold=HOLD, ego_base=0, tilt=None):
 
 
 def run_manual(plan, case, setup, steps):
-    """*_env_step_device + solve_device with a host copy per step: finals, scene rows and statuses
-    [B, steps, ...], the kernels taken."""
-    d = Loop(plan, case)
-    setup(d.pl)
-    scenes, sts, kernels = [], [], set()
-    for _ in range(steps):
-        d.env_step()
-        d.solve()
-        scene, st = d.host("scene", "st")
-        scenes.append(scene)
-        sts.append(st)
-        kernels.add(d.pl.last_kernel())
-    return d.finals(), np.stack(scenes, 1), np.stack(sts, 1), kernels
+    """*_env_step_device + solve_device with a host copy per step, setup(plan) before the first: finals,
+    scene rows and statuses [B, steps, ...], the kernels taken."""
+    cols, kernels, fin = manual(plan, case, steps, setup=lambda d: setup(d.pl))
+    return fin, cols["scene"], cols["status"], kernels
 
 
 def run_loop(plan, case, setup, chunks, record=True):
     """The closed loop in `chunks` calls: finals, the record on the host (or None), the kernels."""
-    d = Loop(plan, case)
-    setup(d.pl)
-    rec = None
-    if record:
-        rec = d.pl.new_loop_record(sum(chunks), 0)
-        d.pl.set_loop_record(rec)
-    kernels = []
-    for c in chunks:
-        d.loop(c)
-        d.stream.synchronize()
-        kernels.append(d.pl.last_kernel())
-    return d.finals(), (None if rec is None else rec.host()), kernels
+    rec, kernels, fin = recorded(plan, case, chunks, predictions=False, attach=record, setup=lambda d: setup(d.pl))
+    return fin, rec, kernels
 
 
 _MANUAL = {}
@@ -147,7 +128,7 @@ def check_against_model(plan, kind, mode, case, paths, scenes, ego_base=0, tilt=
     bmpc_model_eval's p at the row's (x, z) -- the state the step's solve saw, the choice's pre-step
     state -- by obstacle_proposal_common.check_weighted (margin 1e-9, at most 1 % left out, 1e-9 on
     ENV_LOGW)."""
-    sc = S.Scene(kind, len(scenes), case=case)
+    sc = SC.Scene(kind, len(scenes), case=case)
     n = sc.n
     tg = sc.lc_targets(scenes) if kind == "overtake" else None
     smp = abi.make_obstacle_sampling(mode, seed=SEED, hold=HOLD, ego_base=ego_base)

@@ -1,20 +1,21 @@
 """The sampled obstacle of the device closed loops (bmpc_set_obstacle_sampling), host side.
 
 The generator and the choice rule of csrc/bmpc_rng.h as a stand-alone program under the address and
-undefined-behaviour sanitizers (tests/hostsim/obstacle_sampling_host.cpp); the same file as a shared
-library: its draws against bmpc/rng.py, the two scene functions with a sampler against the inverse
+undefined-behaviour sanitizers (tests/hostsim/obstacle_sampling_host.cpp); the scene steps' host build
+(tests/hostsim/scene_host.cpp) as a shared library: its draws against bmpc/rng.py, the two scene functions with a sampler against the inverse
 CDF of oracle.model's branch_eval, the draws' frequencies, and mode 0 against the scene functions'
 former argument list bit for bit; the ctypes mirror, the argument validation and the population
 entries' plumbing.  The GPU side is tests/test_obstacle_sampling_gpu.py."""
 import ctypes as C
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import obstacle_sampling_common as S
+import scene_common as SC
 from bmpc import abi, plan, rng, scenarios
 from common import REPO
 
@@ -35,13 +36,7 @@ def test_host_program_under_sanitizers(tmp_path):
     """The known answers through bmpc_rng.h, the uniform's bounds at the all-ones output, counters with
     g >= 2^32 and seed >= 2^32, the inverse CDF just below and at a partial sum and its m - 1
     fallback, and the choice kept inside an epoch."""
-    exe = tmp_path / "obstacle_sampling_host"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-Wall",
-           "-Wno-unknown-pragmas", *S.INCLUDES, S.SRC, "-o", str(exe)]
-    # the sanitizer runtimes linked into the program where the toolchain has them as archives, else the shared ones
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostbuild.sanitized_program("obstacle_sampling_host.cpp", tmp_path)
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr[-2000:])
 
 
@@ -57,7 +52,7 @@ def test_draws_equal_numpy_restatement():
     ego[:4] = [65535, 2 ** 33 + 5, 0, 2 ** 32]
     epoch[:4] = [0, 1, 2 ** 32 - 1, 4]
     out = np.zeros(n)
-    S.shim().os_uniforms(n, S._p(seed), S._p(ego), S._p(epoch), S._p(out))
+    SC.shim().os_uniforms(n, SC._p(seed), SC._p(ego), SC._p(epoch), SC._p(out))
     want = rng.obstacle_uniform(seed, ego, epoch)
     assert want.shape == (n,) and np.all((want >= 0) & (want < 1))
     np.testing.assert_array_equal(out, want)
@@ -72,9 +67,9 @@ def test_draws_equal_numpy_restatement():
 
 @pytest.fixture(scope="module", params=["overtake", "quadruped"])
 def sampled_run(request):
-    sc = S.Scene(request.param, 65)
+    sc = SC.Scene(request.param, 65)
     smp = abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD)
-    return sc, smp, S.host_run(sc, smp, STEPS)[0]
+    return sc, smp, SC.host_run(sc, STEPS, smp)[0]
 
 
 def test_host_scene_samples_the_models_distribution(sampled_run):
@@ -121,11 +116,11 @@ def test_draw_frequencies(kind, bound):
     1711 / 2385) -- one and the same 4,096 uniforms, so one draw from the statistic's tail, not two; over
     seeds 0..11 the overtake statistic has the spread chi^2 with 2 degrees of freedom should."""
     B = 4096
-    sc = S.Scene(kind, 1)
+    sc = SC.Scene(kind, 1)
     scene = np.repeat(sc.scene0, B, 0)
     pol = abi.policy_array([sc.rows[0]] * B)
     smp = abi.make_obstacle_sampling("model", seed=SEED, hold=1)
-    x, z, _ = sc.host_step(0, scene, pol, None, smp)
+    x, z, _ = SC.host_step(sc, 0, scene, pol, None, smp)
     p = sc.oracle_p(abi.policy_array([sc.rows[0]]), 0, x[0], z[0])
     counts = np.bincount(scene[:, abi.ENV_OBSPOL].astype(int), minlength=sc.m)
     chi2 = float(((counts - B * p) ** 2 / (B * p)).sum())
@@ -140,25 +135,25 @@ def test_draw_frequencies(kind, bound):
 def test_mode_argmax_is_the_unsampled_function(kind):
     """mode 0 with an arbitrary hold and seed, and no sampler at all, reproduce the scene function's
     former argument list bit for bit over the same 12 steps: scene, outputs and policies."""
-    sc = S.Scene(kind, 65)
-    ref, ref_pol = S.host_run(sc, None, STEPS, legacy=True)
+    sc = SC.Scene(kind, 65)
+    ref, ref_pol = SC.host_run(sc, STEPS, arglist=3)
     off = abi.make_obstacle_sampling("argmax", seed=2 ** 63 + 99, hold=5, ego_base=12)
     for smp in (off, None):
-        got, got_pol = S.host_run(sc, smp, STEPS)
+        got, got_pol = SC.host_run(sc, STEPS, smp)
         for a, b in zip(ref, got):
             for k in ("scene", "x", "z", "xref"):
                 np.testing.assert_array_equal(a[k], b[k])
         assert bytes(ref_pol) == bytes(got_pol)
-    sampled = S.host_run(sc, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD), STEPS)[0]
+    sampled = SC.host_run(sc, STEPS, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD))[0]
     assert any((a["scene"][:, abi.ENV_OBSPOL] != b["scene"][:, abi.ENV_OBSPOL]).any() for a, b in zip(ref, sampled))
 
 
 def test_host_scene_shard_invariance():
     """Egos 40..59 of the 65 in a scene batch of their own with ego_base = 40 take the rows they have
     in the whole batch, bit for bit."""
-    sc = S.Scene("overtake", 65)
-    whole = S.host_run(sc, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD), STEPS)[0]
-    part = S.host_run(sc, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD, ego_base=40), STEPS,
+    sc = SC.Scene("overtake", 65)
+    whole = SC.host_run(sc, STEPS, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD))[0]
+    part = SC.host_run(sc, STEPS, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD, ego_base=40),
                       egos=slice(40, 60))[0]
     for a, b in zip(whole, part):
         for k in ("scene", "x", "z", "xref"):
@@ -175,18 +170,11 @@ def test_obstacle_sampling_layout_matches_header(tmp_path):
     code = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmpc.h"\n'
             'int main(){printf("' + "%zu " * (1 + len(FIELDS)) + '%d %d\\n", sizeof(bmpc_obstacle_sampling), ' + offs
             + ', (int)BMPC_OBS_ARGMAX, (int)BMPC_OBS_SAMPLE_MODEL);return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o",
-                           str(tmp_path / "t")])
-    got = list(map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split()))
+    got = hostbuild.header_program(tmp_path, code, cxx=True)   # (C++: the header's own static_assert on the size)
     D = abi.ObstacleSampling
     assert [name for name, _ in D._fields_] == list(FIELDS)
     assert got == [C.sizeof(D)] + [getattr(D, f).offset for f in FIELDS] + [abi.OBS_ARGMAX, abi.OBS_SAMPLE_MODEL]
     assert got[:5] == [24, 0, 4, 8, 16]
-    # the header's own static_assert on the size holds where it is compiled as C++
-    (tmp_path / "t.cpp").write_text('#include "bmpc.h"\nint main(){return 0;}\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"),
-                           str(tmp_path / "t.cpp")])
     assert "static_assert(sizeof(bmpc_obstacle_sampling) == 24" in open(os.path.join(REPO, "include", "bmpc.h")).read()
 
 
@@ -263,8 +251,8 @@ def test_population_entries_plumb_the_sampler():
 def test_lane_change_targets_from_recorded_rows():
     """The GPU tests rebuild the policies in force before a step from recorded scene rows
     (Scene.lc_targets); here against the policy arrays the host scene function actually held."""
-    sc = S.Scene("overtake", 65)
-    run = S.host_run(sc, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD), 40)[0]
+    sc = SC.Scene("overtake", 65)
+    run = SC.host_run(sc, 40, abi.make_obstacle_sampling("model", seed=SEED, hold=HOLD))[0]
     got = sc.lc_targets(np.stack([r["scene"] for r in run], 1))
     want = np.array([[list(r["pol"][e * 3 + 2].p) for r in run] for e in range(65)])
     np.testing.assert_array_equal(got, want)

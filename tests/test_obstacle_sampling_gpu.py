@@ -1,12 +1,12 @@
 """The sampled obstacle of the device closed loops (bmpc_set_obstacle_sampling) on the GPU.
 
 Shapes: overtake N = 6, NB = 1, m = 3 at 65 egos (one past a wave: the one-wave kernels and the fused
-k_loop, selected with BMPC_BLOCK_EGOS=0 / BMPC_LDS_RICH as tests/test_loop_record_gpu.py does) and at
+k_loop, selected with BMPC_BLOCK_EGOS=0 / BMPC_LDS_RICH as tests/loop_common.py does) and at
 3 egos (the small-batch k_solve_blk path); quadruped N = 6, NB = 2 at 65 egos and at 1.  6 steps with
 hold = 2 (3 for the teacher-forced scene kernels).  The egos are the first rows of the batches whose
 loops the existing GPU tests hold to solving (seeded_batch(300, seed=5), test_quad_loop.loop_batch).
 
-Yardsticks: the host build of the scene functions (tests/hostsim/obstacle_sampling_host.cpp, held to
+Yardsticks: the host build of the scene functions (tests/hostsim/scene_host.cpp, held to
 oracle.model and bmpc/rng.py by tests/test_obstacle_sampling.py) for the scene kernels; bit-for-bit
 equality between the launch paths; bmpc/rng.py's inverse CDF of bmpc_model_eval's p at the recorded
 state for the closed loops' choices.  Every case asserts the kernel the plan reports and that every
@@ -15,84 +15,44 @@ import numpy as np
 import pytest
 
 import obstacle_sampling_common as S
+import scene_common as SC
 from bmpc import abi, rng
 from bmpc.scenarios import highway_desc, merge_desc
-from test_loop_record_gpu import BLK, Loop, assert_same_finals, gpu, overtake_case, quad_case, set_path  # noqa: F401
+from loop_common import (PATHS, Loop, assert_all_solved, assert_same_finals, gpu, manual, model_p,  # noqa: F401
+                         overtake_case, quad_case, recorded, set_path)
 
 pytestmark = pytest.mark.gpu
 
 STEPS, HOLD, SEED = 6, 2, 7
-# (BMPC_BLOCK_EGOS, BMPC_LDS_RICH, the per-step solver kernels, the loop's kernels)
-PATHS = {
-    ("overtake", "wave"): (0, 1, (abi.KERNEL_IPM_RICH,), (abi.KERNEL_LOOP_RICH,)),
-    ("overtake", "lean"): (0, 0, (abi.KERNEL_IPM_LEAN,), (abi.KERNEL_LOOP_LEAN,)),
-    ("overtake", "blk"): (None, None, BLK, BLK),              # small batches keep their launches per step
-    ("quadruped", "wave"): (None, 1, (abi.KERNEL_QP_RICH,), (abi.KERNEL_LOOP_RICH,)),
-    ("quadruped", "lean"): (None, 0, (abi.KERNEL_QP_LEAN,), (abi.KERNEL_LOOP_LEAN,)),
-}
 CASES = [("overtake", "wave", 65), ("overtake", "lean", 65), ("overtake", "blk", 3), ("quadruped", "wave", 65),
          ("quadruped", "lean", 65), ("quadruped", "wave", 1)]
 
 
 def scene_of(kind, B, robust=False):
     case = overtake_case(6, 1, B, robust) if kind == "overtake" else quad_case(B)
-    return S.Scene(kind, B, case=case), case
+    return SC.Scene(kind, B, case=case), case
 
 
 def sampler(seed=SEED, hold=HOLD, ego_base=0):
     return abi.make_obstacle_sampling("model", seed=seed, hold=hold, ego_base=ego_base)
 
 
-def assert_all_solved(desc, status):
-    status = np.asarray(status)
-    if desc.controller == abi.CTRL_CVAR:
-        assert np.all((status == 0) | (status == 10)), np.unique(status, return_counts=True)
-    else:
-        assert np.all(status == 1), np.unique(status, return_counts=True)
+def attached(smp):
+    """The setup callback that attaches the sampler (None: none)."""
+    return None if smp is None else lambda d: d.pl.set_obstacle_sampling(smp)
 
 
 def run_loop(plan, case, smp, chunks, record=True):
     """The closed loop in `chunks` calls with the sampler attached: finals, the record on the host, kernels."""
-    d = Loop(plan, case)
-    if smp is not None:
-        d.pl.set_obstacle_sampling(smp)
-    rec = None
-    if record:
-        rec = d.pl.new_loop_record(sum(chunks), 0)
-        d.pl.set_loop_record(rec)
-    kernels = []
-    for c in chunks:
-        d.loop(c)
-        d.stream.synchronize()
-        kernels.append(d.pl.last_kernel())
-    return d.finals(), (None if rec is None else rec.host()), kernels
+    rec, kernels, fin = recorded(plan, case, chunks, predictions=False, attach=record, setup=attached(smp))
+    return fin, rec, kernels
 
 
 def run_manual(plan, case, smp, steps):
     """The same loop as *_env_step_device + solve_device with a host copy per step: finals, the scene
     rows and statuses [B, steps, ...], kernels."""
-    d = Loop(plan, case)
-    if smp is not None:
-        d.pl.set_obstacle_sampling(smp)
-    scenes, sts, kernels = [], [], set()
-    for _ in range(steps):
-        d.env_step()
-        d.solve()
-        scene, st = d.host("scene", "st")
-        scenes.append(scene)
-        sts.append(st)
-        kernels.add(d.pl.last_kernel())
-    return d.finals(), np.stack(scenes, 1), np.stack(sts, 1), kernels
-
-
-def model_p(plan, sc, targets, x, z):
-    """bmpc_model_eval's branch probabilities at (x, z) [B, n] under the scene's policies (overtake: the
-    lane-change targets [B, 4] in force)."""
-    if sc.kind == "overtake":
-        rows = [[r[0], r[1], (abi.POL_LC, tuple(map(float, tg)))] for r, tg in zip(sc.rows, targets)]
-    else:
-        rows = sc.rows
-    return plan.model_eval(sc.desc, rows, x, np.zeros((len(x), sc.desc.d)), z)["p"]
+    cols, kernels, fin = manual(plan, case, steps, setup=attached(smp))
+    return fin, cols["scene"], cols["status"], kernels
 
 
 def check_recorded_choices(plan, sc, smp, scenes, ego_base=0):
@@ -131,7 +91,7 @@ def test_scene_kernel_equals_host_function(gpu, monkeypatch, kind):
     sc, case = scene_of(kind, 65)
     smp = sampler(hold=3)
     steps = 12
-    host = S.host_run(sc, smp, steps)[0]
+    host = SC.host_run(sc, steps, smp)[0]
     d = Loop(gpu, case)
     d.pl.set_obstacle_sampling(smp)
     valid = np.ones(65, bool)
@@ -309,9 +269,9 @@ def test_sampled_populations(gpu, monkeypatch):
         stats, scene, rec = fn(8, 3, obstacle="model", record=True, obstacle_seed=SEED)
         assert rec.kind == kind and np.array_equal(rec.col("scene")[:, -1], scene)
         assert np.all(stats[:, abi.ENVS_SOLVES] == 2)
-        sc = S.Scene(kind, 8, N=20 if kind == "overtake" else 25)      # the entries' own batches and plans
+        sc = SC.Scene(kind, 8, N=20 if kind == "overtake" else 25)      # the entries' own batches and plans
         if kind == "quadruped":
-            sc = S.Scene(kind, 8, case=dict(desc=scenarios.quadruped_desc(), env=abi.make_quad_env(),
+            sc = SC.Scene(kind, 8, case=dict(desc=scenarios.quadruped_desc(), env=abi.make_quad_env(),
                                             scene=rec.col("scene")[:, 0], policies=scenarios.quadruped_policy_rows(8)))
         assert_all_solved(sc.desc, rec.col("status"))
         check_recorded_choices(gpu, sc, sampler(hold=1), rec.col("scene"))

@@ -8,7 +8,7 @@ the argmax picking 1 and picking 0, a return to 0, x_ref clipped at 5 m and not,
 heading within 0.1 m of the goal, each of the two heading wraps), every decision at least 1e-6 from
 its boundary.  No MPC solve is involved; quadruped_n25_nb2.npz pins the controller.
 
-Host (not gpu): the scene function itself, compiled with g++ (tests/hostsim/quad_env_host.cpp), and
+Host (not gpu): the scene function itself, compiled with g++ (tests/hostsim/scene_host.cpp), and
 the package's quadruped_env.Quad_env.step, both fed the fixture's scripted inputs: x / z / xRef to
 1e-9 on every step of every scene (the bar of tests/test_env_host.py: cos / sin / atan2 of a
 different libm), every backup choice equal.
@@ -18,42 +18,19 @@ around real BranchMPCProx solves; the fused k_loop (scene + tree + QP per step) 
 per-step launches bit for bit, LDS-rich and lean; the refusals; bmpc.scenarios.quadruped_population.
 """
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
+import hostbuild
+import scene_common as SC
 from bmpc import abi
 from bmpc.scenarios import (quad_scene, quadruped_desc, quadruped_policy_rows, seeded_quadruped_batch,
                             seeded_quadruped_goals)
-from common import HERE, PKG, REPO, golden
+from common import golden
 
 NAME = "quadruped_scene"
-SRC = os.path.join(HERE, "hostsim", "quad_env_host.cpp")
-SO = os.path.join(HERE, "hostsim", "libbmpc_hostsim_quad_env.so")
-_shim = None
-
-
-def shim():
-    """The host build of the scene function, rebuilt when a source it is compiled from is newer."""
-    global _shim
-    if _shim is None:
-        deps = [SRC, os.path.join(REPO, "include", "bmpc.h")] + [
-            os.path.join(PKG, "csrc", f) for f in ("bmpc_env_quad.h", "bmpc_env.h", "bmpc_model.h", "bmpc_core.h")]
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in deps):
-            tmp = SO + f".{os.getpid()}.tmp"
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas",
-                                   "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(PKG, "csrc"), SRC,
-                                   "-o", tmp])
-            os.replace(tmp, SO)
-        _shim = C.CDLL(SO)
-    return _shim
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def fixture_desc(g, N=None, NB=2):
@@ -67,17 +44,10 @@ def scene_env(g):
 
 def host_env_step(g, t, scene, upred=None, J=None, status=None, iters=None, stats=None):
     """k_env_quad on the host: advances `scene` [B][16] in place; returns x, z, xref."""
-    B = scene.shape[0]
-    desc, env = fixture_desc(g), scene_env(g)
-    mc = np.array(desc.mc[:8], float)
-    pol = abi.policy_array(quadruped_policy_rows(B, float(g["v0"])))
-    x, z, xref = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros((B, 3))
-    up = None if upred is None else np.ascontiguousarray(np.asarray(upred, float).reshape(B, -1))
-    rc = shim().qs_env_step(C.byref(env), _p(mc), C.c_double(desc.dt), desc.N, desc.m, int(t), B, _p(scene), pol,
-                            _p(up), 0 if up is None else up.shape[1], _p(J), _p(status), _p(iters), _p(x), _p(z),
-                            _p(xref), _p(stats))
-    assert rc == 0
-    return x, z, xref
+    desc = fixture_desc(g)
+    sc = types.SimpleNamespace(kind="quadruped", n=3, env=scene_env(g), desc=desc, mc=np.array(desc.mc[:8], float))
+    pol = abi.policy_array(quadruped_policy_rows(scene.shape[0], float(g["v0"])))
+    return SC.host_step(sc, t, scene, pol, upred, solve=(J, status, iters, stats))
 
 
 def check_scene_step(g, t, scene, x, z, xref):
@@ -125,9 +95,7 @@ def test_quad_env_desc_layout_matches_header(tmp_path):
     code = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmpc.h"\n'
             'int main(){printf("%zu %zu %zu\\n", sizeof(bmpc_quad_env_desc), offsetof(bmpc_quad_env_desc, lookahead),'
             ' offsetof(bmpc_quad_env_desc, near));return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
-    size, a, b = map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split())
+    size, a, b = hostbuild.header_program(tmp_path, code)
     D = abi.QuadEnvDesc
     assert (size, a, b) == (C.sizeof(D), D.lookahead.offset, D.near.offset)
 

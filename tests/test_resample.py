@@ -11,11 +11,11 @@ import ctypes as C
 import inspect
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import resample_common as R
 from bmpc import abi, montecarlo, plan, resample, rng, scenarios
 from common import REPO
@@ -28,13 +28,7 @@ def test_host_program_under_sanitizers(tmp_path):
     """The rule over the batch sizes and weight families with its properties, the conversion's rounding,
     the refusals, and synthetic slabs gathered through a permutation, a broadcast, clamped entries and
     the rule's own arrangement, compiled with -fsanitize=address,undefined and run once."""
-    exe = tmp_path / "resample_host"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-Wall",
-           "-Wno-unknown-pragmas", *R.INCLUDES, R.SRC, "-o", str(exe)]
-    # the sanitizer runtimes linked into the program where the toolchain has them as archives, else the shared ones
-    if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
-        subprocess.check_call(cmd)
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    r = hostbuild.sanitized_program("resample_host.cpp", tmp_path)
     assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr[-2000:])
 
 
@@ -45,17 +39,13 @@ def test_resample_desc_layout_matches_header(tmp_path):
             'int main(){printf("' + "%zu " * (2 + len(fields)) + '%d %d %d\\n", sizeof(bmpc_resample_desc), '
             + offs + ', sizeof(bmpc_ego_buffers), (int)BMPC_RESAMPLE_NINFO, (int)BMPC_RESAMPLE_SYSTEMATIC, '
             '(int)BMPC_RESAMPLE_MAX_BATCH);return 0;}\n')
-    (tmp_path / "t.c").write_text(code)
-    subprocess.check_call(["gcc", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")])
-    got = list(map(int, subprocess.check_output([str(tmp_path / "t")]).decode().split()))
+    got = hostbuild.header_program(tmp_path, code, cxx=True)
     D = abi.ResampleDesc
     assert [n for n, _ in D._fields_] == list(fields)
     assert got == [C.sizeof(D)] + [getattr(D, f).offset for f in fields] + [
         C.sizeof(abi.EgoBuffers), abi.RESAMPLE_NINFO, abi.RESAMPLE_SYSTEMATIC, abi.RESAMPLE_MAX_BATCH]
     assert got == [32, 0, 4, 8, 16, 24, 72, 8, 0, 1 << 20]
     assert [n for n, _ in abi.EgoBuffers._fields_] == ["scene", "upred", "x", "z", "xref", "J", "status", "iters", "stats"]
-    (tmp_path / "t.cpp").write_text('#include "bmpc.h"\nint main(){return 0;}\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(REPO, "include"), str(tmp_path / "t.cpp")])
     assert "static_assert(sizeof(bmpc_resample_desc) == 32" in open(os.path.join(REPO, "include", "bmpc.h")).read()
 
 

@@ -2,7 +2,7 @@
 bmpc_resample_device).
 
 Shapes follow the obstacle tests': overtake N = 6, NB = 1, m = 3 and quadruped N = 6, NB = 2, m = 2;
-the launch paths are selected as tests/test_loop_record_gpu.py does.
+the launch paths are selected as tests/loop_common.py does.
 
 Yardsticks: bmpc/resample.py's exact integer rule fed the device's own integer weights k (equal
 integers, no tolerance); an un-gathered run of the same plan on the same launch path (bit for bit: a
@@ -17,8 +17,7 @@ import resample_common as R
 from bmpc import abi, resample, scenarios
 from bmpc._lib import lib
 from bmpc.scenarios import highway_desc, merge_desc, quadruped_desc
-from test_loop_record_gpu import BLK, Loop, gpu, overtake_case, quad_case, set_path  # noqa: F401
-from test_obstacle_sampling_gpu import PATHS, assert_all_solved
+from loop_common import FINALS, PATHS, Loop, assert_all_solved, gpu, overtake_case, quad_case, set_path  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -113,7 +112,6 @@ def test_threshold_on_each_side(gpu, B):
 GATHER_B = 8
 GATHER_MAP = np.array([0, 0, 0, 4, 3, 5, 6, 5], np.int32)   # a broadcast of ego 0, a swap 3 <-> 4, 5 also into 7; 5, 6 fixed
 K1 = K2 = 4
-FINALS = ("scene", "up", "J", "st", "it", "stats", "x", "z", "xref")
 
 
 def run_segments(plan, case, amap, setup=None, between=None):

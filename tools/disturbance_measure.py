@@ -64,8 +64,7 @@ def run(shape, egos, steps, warmup, seed, sigmas=None):
             pl.set_policies(scenarios.merge_policy_rows(egos))
             pl.set_merge_scene(abi.make_merge_env(), *scenarios.merge_lane_ref())
             loop = pl.merge_loop_device
-        scene0 = np.zeros((egos, abi.ENV_STRIDE))
-        scene0[:, abi.ENV_X:abi.ENV_X + 4], scene0[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
+        scene0 = scenarios._overtake_scene(x, z)
     if sigmas is not None:
         pl.set_disturbance(*sigmas, seed=seed)
     n, d = pl.desc.n, pl.desc.d

@@ -25,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "belief-planning_amd")]
 
 from bmpc import abi, montecarlo, plan  # noqa: E402
-from bmpc.scenarios import (highway_desc, highway_policy_rows, quad_scene, quadruped_desc,  # noqa: E402
+from bmpc.scenarios import (_overtake_scene, highway_desc, highway_policy_rows, quad_scene, quadruped_desc,  # noqa: E402
                             quadruped_policy_rows, seeded_batch, seeded_quadruped_batch, seeded_quadruped_goals)
 
 SHAPES = {"overtake": dict(egos=4096, steps=8), "quadruped": dict(egos=1024, steps=6)}
@@ -44,8 +44,7 @@ class Population:
             x, z, _, tgt = seeded_batch(egos, seed)
             self.pl = pl = plan.BatchPlan(highway_desc(), egos)
             pl.set_policies(highway_policy_rows(tgt))
-            scene = np.zeros((egos, abi.ENV_STRIDE))
-            scene[:, abi.ENV_X:abi.ENV_X + 4], scene[:, abi.ENV_Z:abi.ENV_Z + 4] = x, z
+            scene = _overtake_scene(x, z)
             self.env, self.loop = abi.make_env(), pl.loop_device
         else:
             x, z, _ = seeded_quadruped_batch(egos, seed)
