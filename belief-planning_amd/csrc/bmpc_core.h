@@ -12,6 +12,22 @@
 
 #include "bmpc.h"
 
+// BMPC_PHASE_NOCSR (per translation unit; a .hip file may define it before its includes): the
+// phase calls are never marked as tail calls.  The compiler drops a function's callee-saved
+// register saves only when it has local linkage, is not recursive, has no address taken and no
+// call to it carries the tail marker -- which the optimiser puts on almost every direct call.
+// Without the marker the phases lose their prologue / epilogue scratch round trips and their
+// callers learn from the propagated register masks what each callee clobbers.
+// The macro is defined in every build: the host build has no such attribute, but the call
+// structure that goes with the mode (BMPC_THIN_CALLERS, bmpc_ipm.h) follows this default there too.
+#ifndef BMPC_PHASE_NOCSR
+#define BMPC_PHASE_NOCSR 1
+#endif
+#if BMPC_PHASE_NOCSR && defined(__HIP_DEVICE_COMPILE__)
+#define BMPC_FN_CALLS __attribute__((not_tail_called))
+#else
+#define BMPC_FN_CALLS
+#endif
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define BMPC_HD __host__ __device__ __forceinline__
@@ -20,7 +36,7 @@
 #if defined(BMPC_INLINE_ALL)
 #define BMPC_FN __host__ __device__ __forceinline__
 #else
-#define BMPC_FN __host__ __device__ __attribute__((noinline))
+#define BMPC_FN __host__ __device__ __attribute__((noinline)) BMPC_FN_CALLS
 #endif
 #else
 #define BMPC_HD inline

@@ -58,6 +58,14 @@
 #ifndef BMPC_FLAT_PAIR
 #define BMPC_FLAT_PAIR 1     // 1: the IPM loop calls the pair's coupling solve and refinement directly
 #endif
+#ifndef BMPC_THIN_CALLERS
+#define BMPC_THIN_CALLERS BMPC_PHASE_NOCSR   // 1: a function that calls phases does no long work of its own -- a KKT
+                                // solve is its front part (the W^-1, G' and tree-solve calls), its back half as a
+                                // leaf and the refinement, each called by the IPM loop; the refinements call their
+                                // correction's tree solve and its back half (a leaf).  Without callee-saved saves
+                                // (BMPC_PHASE_NOCSR) a caller spills what it holds across a call, so the long
+                                // passes sit in leaves.  Same operations in the same order as =0.
+#endif
 #ifndef BMPC_IPM_LEAN_PASSES
 #define BMPC_IPM_LEAN_PASSES 1  // 1: the IPM iteration without the passes and re-reads its result does not need (same
                                 // values from the same expressions; 0: the separate passes, kept for the A/B and
@@ -2780,12 +2788,18 @@ BMPC_HD int gvar(CPlan& P, int i) { return i == P.ng - 1 ? P.oJ : P.oRho + i; }
 // (gk + nc nv: the c-direction and affine solves' G'W^-2 r3 + r1), the eq-space slots after the
 // nc zero vectors (bvec, ry), solutions to the slots after the Woodbury columns (x1 / x2,
 // y1 / y2) -- the Riccati data are read once for all of them (Layout, bmpc_plan.cpp).
+#if BMPC_THIN_CALLERS
+// (thin callers: kkt_coupling is the columns' tree solve and then kkt_coupling_lu -- the coupling
+// matrix and its LU, which holds nothing across the tree solve)
+template <class X, int NX, int NU>
+BMPC_FN bool kkt_coupling_lu(const X ex, const Ctx Cin);
+#endif
 template <class X, int NX, int NU>
 BMPC_FN bool kkt_coupling(const X ex, const Ctx Cin, int extra) {
   const Ctx C = Cin.uniform();
   CPlan& P = *C.P;
   CLayout& L = *C.L;
-  BMPC_PROF(C.ws, L, PROF_COUPLING);
+  BMPC_PROF(C.ws, L, PROF_COUPLING);   // (thin callers: the scope still spans the tree solve and kkt_coupling_lu)
   gdouble* ws = C.ws;
   const int nc = P.ncones;
   BMPC_TIC(t_cts);
@@ -2796,6 +2810,17 @@ BMPC_FN bool kkt_coupling(const X ex, const Ctx Cin, int extra) {
     tree_solve<X, NX, NU>(ex, C, nc + extra, ws + L.gk, P.nv, ws + L.zeros, P.neq, ws + L.colk, P.nv, ws + L.colnu,
                           P.neq, nc);
   BMPC_TOC(C.ws, L, PROF_CTS, t_cts);
+#if BMPC_THIN_CALLERS
+  return kkt_coupling_lu<X, NX, NU>(ex, C);
+}
+template <class X, int NX, int NU>
+BMPC_FN bool kkt_coupling_lu(const X ex, const Ctx Cin) {
+  const Ctx C = Cin.uniform();
+  CPlan& P = *C.P;
+  CLayout& L = *C.L;
+  gdouble* ws = C.ws;
+  const int nc = P.ncones;
+#endif
   BMPC_TIC(t_cdot);
   const int ng = P.ng, nb = P.bdim, ns = P.nsm;
   auto* M = coup_mem(ex, ws, L, P, P.lds_M);
@@ -3149,9 +3174,38 @@ template <class X, int NX, int NU>
 BMPC_HD void kkt_refine(const X ex, const Ctx& C, const gdouble* r1, const gdouble* r2, const gdouble* r3h,
                         gdouble* dx, gdouble* dy, gdouble* dz, int nitref);
 
+#if BMPC_THIN_CALLERS
+// The back half of refinement correction j (kkt_refine: j = 0; kkt_refine_pair: its direction) as a
+// leaf: kkt_solve_once<R3ZERO>'s kkt_back on the correction's slots, after the caller's tree solve.
+template <class X, int NX, int NU>
+BMPC_FN void refine_back_one(const X ex, const Ctx Cin, int j) {
+  const Ctx C = Cin.uniform();
+  j = ex.uniform(j != 0) ? 1 : 0;
+  CPlan& P = *C.P;
+  CLayout& L = *C.L;
+  gdouble* ws = C.ws;
+  const size_t nv = P.nv, neq = P.neq, nr = P.nrows;
+  kkt_back<X, NX, NU, true>(ex, C, ws + L.k_e1 + j * nv, ws + L.k_e2 + j * neq, nullptr, ws + L.k_cx + j * nv,
+                            ws + L.k_cy + j * neq, ws + L.k_cz + j * nr, false);
+}
+// refinement correction j: K [cx; cy; cz] = [e1; e2; 0] (kkt_solve_once<R3ZERO> as its two calls)
+template <class X, int NX, int NU>
+BMPC_HD void refine_correction(const X ex, const Ctx& C, int j) {
+  CPlan& P = *C.P;
+  CLayout& L = *C.L;
+  gdouble* ws = C.ws;
+  const size_t nv = P.nv, neq = P.neq;
+  tree_solve<X, NX, NU>(ex, C, 1, ws + L.k_e1 + j * nv, 0, ws + L.k_e2 + j * neq, 0, ws + L.k_cx + j * nv, 0,
+                        ws + L.k_cy + j * neq, 0);
+  refine_back_one<X, NX, NU>(ex, C, j);
+}
+#endif
+
 // Solve [0 A' G'; A 0 0; G 0 -W^2] [dx; dy; dz] = [r1; r2; r3]: W-scaled solve with
 // iterative refinement on the scaled residual (well conditioned, unlike the W^2 form whose
 // residual is dominated by the rounding of W^2 dz near the boundary).
+// (With BMPC_THIN_CALLERS the IPM loop calls kkt_solve_flat's parts instead; kkt_solve stays for
+// BMPC_THIN_CALLERS=0 and for the phase-per-kernel tools build, experimental/bmpc_ipm_ph.h.)
 template <class X, int NX, int NU>
 BMPC_FN void kkt_solve(const X ex, const Ctx Cin, const gdouble* r1, const gdouble* r2,
                        const gdouble* r3, gdouble* dx, gdouble* dy, gdouble* dz, int nitref) {
@@ -3169,6 +3223,59 @@ BMPC_FN void kkt_solve(const X ex, const Ctx Cin, const gdouble* r1, const gdoub
   if (fin) return;
   kkt_refine<X, NX, NU>(ex, C, r1, r2, r3h, dx, dy, dz, nitref);
 }
+
+#if BMPC_THIN_CALLERS
+// kkt_solve as the calls of its parts (the IPM loop's kkt_solve_flat): the front part forms
+// r3h = W^-1 r3, G'W^-1 r3h + r1 and the tree solution in (dx, dy); the back half (a leaf) is
+// kkt_back on them; the refinement a call of its own.  (BMPC_PROFILE builds: each part opens
+// PROF_KKT, whose slot accumulates cycles, so the slot holds the sum of the three parts -- kkt_solve's
+// span less the cycles between the calls; solves are counted by PROF_NSOLVE, once, in the front.)
+template <class X, int NX, int NU>
+BMPC_FN void kkt_solve_front(const X ex, const Ctx Cin, const gdouble* r1, const gdouble* r2, const gdouble* r3,
+                             gdouble* dx, gdouble* dy) {
+  const Ctx C = Cin.uniform();
+  r1 = uniform_ptr(r1), r2 = uniform_ptr(r2), r3 = uniform_ptr(r3), dx = uniform_ptr(dx), dy = uniform_ptr(dy);
+  CLayout& L = *C.L;
+  BMPC_PROF(C.ws, L, PROF_KKT);
+  gdouble* ws = C.ws;
+  gdouble* tz = ws + L.k_nv0;
+  apply_Winv2(ex, C, r3, ws + L.k_t3, ws + L.k_r0);
+  BMPC_COUNT(ws, L, PROF_NSOLVE);
+  apply_GT<X, NX, NU>(ex, C, ws + L.k_r0, tz, r1);
+  tree_solve<X, NX, NU>(ex, C, 1, tz, 0, r2, 0, dx, 0, dy, 0);
+}
+template <class X, int NX, int NU>
+BMPC_FN void kkt_solve_back(const X ex, const Ctx Cin, const gdouble* r2, gdouble* dx, gdouble* dy, gdouble* dz,
+                            bool fin) {
+  const Ctx C = Cin.uniform();
+  fin = ex.uniform(fin);
+  CLayout& L = *C.L;
+  BMPC_PROF(C.ws, L, PROF_KKT);
+  kkt_back<X, NX, NU, false>(ex, C, C.ws + L.k_nv0, r2, C.ws + L.k_t3, dx, dy, dz, fin);
+}
+template <class X, int NX, int NU>
+BMPC_FN void kkt_refine_call(const X ex, const Ctx Cin, const gdouble* r1, const gdouble* r2, gdouble* dx, gdouble* dy,
+                             gdouble* dz, int nitref) {
+  const Ctx C = Cin.uniform();
+  r1 = uniform_ptr(r1), r2 = uniform_ptr(r2), dx = uniform_ptr(dx), dy = uniform_ptr(dy), dz = uniform_ptr(dz);
+  BMPC_PROF(C.ws, *C.L, PROF_KKT);
+  kkt_refine<X, NX, NU>(ex, C, r1, r2, C.ws + C.L->k_t3, dx, dy, dz, nitref);
+}
+template <class X, int NX, int NU>
+BMPC_HD void kkt_solve_flat(const X ex, const Ctx& C, const gdouble* r1, const gdouble* r2, const gdouble* r3,
+                            gdouble* dx, gdouble* dy, gdouble* dz, int nitref) {
+  kkt_solve_front<X, NX, NU>(ex, C, r1, r2, r3, dx, dy);
+  const bool fin = ex.uniform(nitref == 0);
+  kkt_solve_back<X, NX, NU>(ex, C, r2, dx, dy, dz, fin);   // dz holds dzh until the refinement's end
+  if (!fin) kkt_refine_call<X, NX, NU>(ex, C, r1, r2, dx, dy, dz, nitref);
+}
+#else
+template <class X, int NX, int NU>
+BMPC_HD void kkt_solve_flat(const X ex, const Ctx& C, const gdouble* r1, const gdouble* r2, const gdouble* r3,
+                            gdouble* dx, gdouble* dy, gdouble* dz, int nitref) {
+  kkt_solve<X, NX, NU>(ex, C, r1, r2, r3, dx, dy, dz, nitref);
+}
+#endif
 
 // Iterative refinement of a W-scaled solve on its scaled residual (nitref > 0 rounds at most),
 // then dz = W^-1 dzh in place (dz holds dzh on entry).
@@ -3224,7 +3331,11 @@ BMPC_HD void kkt_refine(const X ex, const Ctx& C, const gdouble* r1, const gdoub
       if (ex.uniform(prev < BMPC_REF_STALL * err)) break;   // stalled: kept, no further round
     }
     prev = err;
+#if BMPC_THIN_CALLERS
+    refine_correction<X, NX, NU>(ex, C, 0);
+#else
     kkt_solve_once<X, NX, NU, true>(ex, C, e1, e2, nullptr, cx, cy, cz, false, false);
+#endif
     lane_batch<16>(ex, 0, P.nv, [&](int i) { return dx[i] + cx[i]; }, [&](int i, double v) { dx[i] = v; });
     lane_batch(ex, 0, P.neq, [&](int i) { return dy[i] + cy[i]; }, [&](int i, double v) { dy[i] = v; });
     lane_batch<16>(ex, 0, P.nrows, [&](int i) { return dz[i] + cz[i]; }, [&](int i, double v) { dz[i] = v; });
@@ -3255,6 +3366,7 @@ BMPC_FN void refine_back_pair(const X ex, const Ctx Cin) {
   kkt_back_pair<X, NX, NU, true>(ex, C, ws + L.k_e1, ws + L.k_e2, nullptr, cx, cy, cz, ws + L.k_e1 + nv,
                                  ws + L.k_e2 + neq, nullptr, cx + nv, cy + neq, cz + nr, false);
 }
+// (used with BMPC_THIN_CALLERS=0 only: the thin callers' refine_correction takes its place)
 template <class X, int NX, int NU>
 BMPC_FN void refine_solve_one(const X ex, const Ctx Cin, int j) {
   const Ctx C = Cin.uniform();
@@ -3273,6 +3385,12 @@ BMPC_FN void kkt_refine_pair(const X ex, const Ctx Cin, const gdouble* r1a, cons
                              gdouble* dxa, gdouble* dya, gdouble* dza, const gdouble* r1b, const gdouble* r2b,
                              const gdouble* r3hb, gdouble* dxb, gdouble* dyb, gdouble* dzb, int nitref) {
   const Ctx C = Cin.uniform();
+#if BMPC_THIN_CALLERS   // the twelve vectors as scalar pointers: SGPRs across the calls, not 24 VGPRs spilled around each
+  r1a = uniform_ptr(r1a), r2a = uniform_ptr(r2a), r3ha = uniform_ptr(r3ha);
+  dxa = uniform_ptr(dxa), dya = uniform_ptr(dya), dza = uniform_ptr(dza);
+  r1b = uniform_ptr(r1b), r2b = uniform_ptr(r2b), r3hb = uniform_ptr(r3hb);
+  dxb = uniform_ptr(dxb), dyb = uniform_ptr(dyb), dzb = uniform_ptr(dzb);
+#endif
   CPlan& P = *C.P;
   CLayout& L = *C.L;
   gdouble* ws = C.ws;
@@ -3345,7 +3463,9 @@ BMPC_FN void kkt_refine_pair(const X ex, const Ctx Cin, const gdouble* r1a, cons
 #endif
     } else {
       const int j = on[0] ? 0 : 1;
-#if BMPC_REFINE_CALLS
+#if BMPC_THIN_CALLERS
+      refine_correction<X, NX, NU>(ex, C, j);
+#elif BMPC_REFINE_CALLS
       refine_solve_one<X, NX, NU>(ex, C, j);
 #else
       kkt_solve_once<X, NX, NU, true>(ex, C, ws + L.k_e1 + j * nv, ws + L.k_e2 + j * neq, nullptr, cx + j * nv,
@@ -3799,7 +3919,7 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
   }
   lane_batch<16>(ex, 0, nv, [&](int i) { return 0.0; }, [&](int i, double v) { tA[i] = v; });
   ex.sync();
-  kkt_solve<X, NX, NU>(ex, C, tA, bv, hv, x, y2, z2, BMPC_NITREF_INIT);
+  kkt_solve_flat<X, NX, NU>(ex, C, tA, bv, hv, x, y2, z2, BMPC_NITREF_INIT);
   // s = ge bring2cone(-ge z)  (ECOS: s~ = bring2cone(-z~), z~ = ge z, s = ge s~)
   lane_batch<16>(ex, 0, nr, [&](int i) { return -(BMPC_EQUIL ? gq[i] : 1.0) * z2[i]; }, [&](int i, double v) { ra[i] = v; });
   ex.sync();
@@ -3814,7 +3934,7 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
   lane_batch(ex, 0, neq, [&](int i) { return 0.0; }, [&](int i, double v) { ya[i] = v; });
   lane_batch<16>(ex, 0, nr, [&](int i) { return 0.0; }, [&](int i, double v) { ra[i] = v; });
   ex.sync();
-  kkt_solve<X, NX, NU>(ex, C, ej, ya, ra, x2, y, z2, BMPC_NITREF_INIT);
+  kkt_solve_flat<X, NX, NU>(ex, C, ej, ya, ra, x2, y, z2, BMPC_NITREF_INIT);
   // z = bring2cone(ge z) / ge
   if (BMPC_EQUIL) {
     lane_batch<16>(ex, 0, nr, [&](int i) { return gq[i] * z2[i]; }, [&](int i, double v) { z2[i] = v; });
@@ -4029,7 +4149,7 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
       lane_batch<16>(ex, 0, nv, [&](int i) { return -eta1 * rx[i]; }, [&](int i, double v) { tA[i] = v; });
       lane_batch(ex, 0, neq, [&](int i) { return eta1 * ry[i]; }, [&](int i, double v) { ya[i] = v; });
       ex.sync();
-      kkt_solve<X, NX, NU>(ex, C, tA, ya, rb, x2, y2, z2, nref);
+      kkt_solve_flat<X, NX, NU>(ex, C, tA, ya, rb, x2, y2, z2, nref);
       const double dk_c = -kap * tau - dtau_a * dkap_a + sigma * mu;
       dtau = (eta1 * rt + dk_c / tau + x2[P.oJ] + dot2(ex, bv, y2, neq, hv, z2, nr)) / den;
       double nonfinite = 0.0;   // the step's finiteness check, taken in the pass that forms dx
