@@ -7,6 +7,11 @@ libbmpc.so: seeded random QPs with every row class OSQP accepts (equalities, one
 two-sided, free rows), an unconstrained problem, the belief-MPC problems the reference's
 own PredictiveControllers assembled (tests/golden/belief_*.npz), the optimality conditions
 of the returned dual, and the host analysis' error paths.
+
+Which factorisation path these problems take falls out of what the ordering makes of a random
+dense A.  tests/test_bandqp_paths.py pins every path (blocked / column-at-a-time in LDS, the ring
+window with W <= 64 and W > 64) at its switch-over shapes with the problems of
+tests/bandqp_families.py, and reuses random-QP helpers, the oracle wrapper and check_kkt from here.
 """
 import numpy as np
 import pytest
