@@ -134,6 +134,7 @@ _SIGS = {
     "bmpc_set_obstacle_sampling": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_set_obstacle_proposal": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_set_disturbance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bmpc_set_observation": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_population_ancestors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "bmpc_gather_egos": (C.c_int, [C.c_void_p] * 4),
     "bmpc_resample_device": (C.c_int, [C.c_void_p] * 6),

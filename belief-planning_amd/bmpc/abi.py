@@ -225,6 +225,40 @@ def make_disturbance(sigma_ego=None, sigma_obs=None, seed=0, ego_base=0, law=DIS
     return D
 
 
+OBSERVE_NONE, OBSERVE_IH4 = 0, 1   # bmpc_observation.law (include/bmpc.h BMPC_OBSERVE_*)
+
+
+class Observation(C.Structure):
+    """bmpc_observation: the observation noise on the states the closed loops' scene steps hand to the
+    next solve (bmpc_set_observation; the draws are bmpc.rng.observation's).  152 bytes."""
+    _fields_ = [("law", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("ego_base", C.c_int64),
+                ("sigma_x", C.c_double * MAX_N), ("sigma_z", C.c_double * MAX_N)]
+
+
+def make_observation(sigma_x=None, sigma_z=None, seed=0, ego_base=0, law=OBSERVE_IH4, n=None):
+    """Validated bmpc_observation.  sigma_x / sigma_z: the standard deviation per state component of
+    the observed ego / obstacle state (None: zeros; finite and >= 0, at most MAX_N entries -- n when
+    the plan's state dimension is given), a seed of 64 bits, ego_base >= 0 the global index of the
+    plan's ego 0, law abi.OBSERVE_IH4 or abi.OBSERVE_NONE."""
+    if int(law) not in (OBSERVE_NONE, OBSERVE_IH4):
+        raise ValueError("law: abi.OBSERVE_NONE or abi.OBSERVE_IH4")
+    if int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if int(ego_base) != ego_base or not 0 <= int(ego_base) < 2 ** 63:
+        raise ValueError("ego_base must be an integer of at least 0")
+    O = Observation()
+    O.law, O.seed, O.ego_base = int(law), int(seed), int(ego_base)
+    lim = MAX_N if n is None else int(n)
+    for name, sig in (("sigma_x", sigma_x), ("sigma_z", sigma_z)):
+        s = np.zeros(0) if sig is None else np.atleast_1d(np.asarray(sig, dtype=np.float64))
+        if s.ndim != 1 or s.size > lim:
+            raise ValueError(f"{name} must hold at most {lim} entries (one per state component), got shape {s.shape}")
+        if not (np.all(np.isfinite(s)) and np.all(s >= 0)):
+            raise ValueError(f"every {name} entry must be finite and >= 0")
+        _fill(getattr(O, name), s)
+    return O
+
+
 RESAMPLE_SYSTEMATIC = 0        # bmpc_resample_desc.scheme (include/bmpc.h BMPC_RESAMPLE_*)
 RESAMPLE_NINFO = 8             # doubles of the info vector (R_* slots)
 RESAMPLE_MAX_BATCH = 1 << 20

@@ -372,6 +372,29 @@ class BatchPlan:
         check(lib().bmpc_set_disturbance(self._h, None if struct is None else C.byref(struct)), "bmpc_set_disturbance")
         self.disturbance = struct
 
+    # ---- the scenes' observation noise ---------------------------------------------------------
+    def set_observation(self, sigma_x=None, sigma_z=None, seed=0, ego_base=0):
+        """Observation noise in the plan's closed loops (bmpc_set_observation): the solve of
+        closed-loop step t of row e is handed
+        ``x + sigma_x * bmpc.rng.observation(seed, ego_base + e, t, "ego", n)`` and
+        ``z + sigma_z * bmpc.rng.observation(seed, ego_base + e, t, "obstacle", n)`` instead of the
+        scene's true states x, z -- the disturbance's unit-variance bounded variate per component, the
+        product rounded before it is added.  sigma_x / sigma_z: up to n standard deviations >= 0 (None:
+        zeros; a zero component makes no draw and passes through).  Only the solve's two inputs change
+        (the loop entries' x / z buffers hold the observed vectors): the scene row, the recorder, the
+        collision rule, the obstacle's choice, the statistics, x_ref and the merge scene's S / bx stay
+        on the truth.  All three scenes, both launch paths and the single-step entries obey it; a shard
+        passes ego_base=lo.  sigma_x=None, sigma_z=None detaches.  Also takes an abi.Observation as
+        `sigma_x`."""
+        if isinstance(sigma_x, abi.Observation):
+            struct = sigma_x
+        elif sigma_x is None and sigma_z is None:
+            struct = None
+        else:
+            struct = abi.make_observation(sigma_x, sigma_z, seed, ego_base, n=int(self.desc.n))
+        check(lib().bmpc_set_observation(self._h, None if struct is None else C.byref(struct)), "bmpc_set_observation")
+        self.observation = struct
+
     # ---- resampling a weighted population ------------------------------------------------------
     def _ego_buffers(self, buffers):
         return buffers if isinstance(buffers, abi.EgoBuffers) else abi.make_ego_buffers(buffers)

@@ -5,15 +5,18 @@ A draw is addressed by (seed, global ego, epoch), never consumed: anyone can rep
 choice an obstacle made at closed-loop step t from ``obstacle_uniform(seed, ego_base + e, t // hold)``
 and the model's branch probabilities at that step's state (``inverse_cdf``), without a GPU.  The
 actuation disturbance (``BatchPlan.set_disturbance``) is addressed the same way: the inputs applied
-after step t are ``nominal + sigma * disturbance(seed, ego_base + e, t, vehicle, d)``."""
+after step t are ``nominal + sigma * disturbance(seed, ego_base + e, t, vehicle, d)``.  So is the
+observation noise (``BatchPlan.set_observation``): the solve of step t sees
+``true state + sigma * observation(seed, ego_base + e, t, vehicle, n)``."""
 from __future__ import annotations
 
 import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
-PURPOSE_OBSTACLE_POLICY = 0      # counter word 3; 1 is bmpc.resample's, 2-7 are reserved
+PURPOSE_OBSTACLE_POLICY = 0      # counter word 3; 1 is bmpc.resample's, 2-7 are reserved, 8-15 and 16-31 below
 DISTURBANCE_PURPOSE = {"obstacle": 8, "ego": 12}   # ... + c for component c of the vehicle's input
+OBSERVATION_PURPOSE = {"obstacle": 16, "ego": 24}   # ... + c for component c of the vehicle's observed state
 DISTURBANCE_SCALE = float.fromhex("0x1.bb67ae8584caap-32")   # sqrt(3) / 2^32
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
@@ -71,6 +74,18 @@ def ih4(o):
     return s.astype(np.float64) * DISTURBANCE_SCALE
 
 
+def _ih4_at(seed, ego, step, purpose0, k):
+    """ih4 [..., k] at the counters {lo32(ego), hi32(ego), step, purpose0 + c}, c < k, key = seed."""
+    s, g, t = np.broadcast_arrays(_u64(seed, "seed"), _u64(ego, "ego"), _u64(step, "step"))
+    if t.size and t.max() >= 2 ** 32:
+        raise ValueError("step must fit 32 bits")
+    s, g, t = (np.broadcast_to(a[..., None], a.shape + (int(k),)) for a in (s, g, t))
+    purpose = np.broadcast_to(np.arange(int(k), dtype=np.uint64) + np.uint64(purpose0), g.shape)
+    counter = np.stack([g & _MASK, g >> _S32, t, purpose], axis=-1)
+    key = np.stack([s & _MASK, s >> _S32], axis=-1)
+    return ih4(philox4x32(counter, key))
+
+
 def disturbance(seed, ego, step, vehicle, d):
     """xi [..., d] of the actuation disturbance (``BatchPlan.set_disturbance``): seed its 64-bit
     seed, ego the GLOBAL ego index (the plan's ego_base + its row), step the closed-loop step t
@@ -81,14 +96,22 @@ def disturbance(seed, ego, step, vehicle, d):
         raise ValueError(f"vehicle {vehicle!r}: one of {sorted(DISTURBANCE_PURPOSE)}")
     if int(d) != d or not 1 <= int(d) <= 4:
         raise ValueError("d must be an integer in 1..4")
-    s, g, t = np.broadcast_arrays(_u64(seed, "seed"), _u64(ego, "ego"), _u64(step, "step"))
-    if t.size and t.max() >= 2 ** 32:
-        raise ValueError("step must fit 32 bits")
-    s, g, t = (np.broadcast_to(a[..., None], a.shape + (int(d),)) for a in (s, g, t))
-    purpose = np.broadcast_to(np.arange(int(d), dtype=np.uint64) + np.uint64(DISTURBANCE_PURPOSE[vehicle]), g.shape)
-    counter = np.stack([g & _MASK, g >> _S32, t, purpose], axis=-1)
-    key = np.stack([s & _MASK, s >> _S32], axis=-1)
-    return ih4(philox4x32(counter, key))
+    return _ih4_at(seed, ego, step, DISTURBANCE_PURPOSE[vehicle], d)
+
+
+def observation(seed, ego, step, vehicle, n):
+    """xi [..., n] of the observation noise (``BatchPlan.set_observation``): seed its 64-bit seed, ego
+    the GLOBAL ego index (the plan's ego_base + its row), step the closed-loop step t whose solve sees
+    the observation, vehicle "obstacle" or "ego", n the state dimension (<= 8).  The state handed to
+    the solve of step t is ``true state + sigma * observation(...)``, the product rounded before it is
+    added -- what NumPy computes; a component with sigma == 0 passes through
+    (``np.where(sigma != 0, ...)``).  The variate is ``disturbance``'s, at purposes of its own.
+    Vectorised like ``obstacle_uniform``."""
+    if vehicle not in OBSERVATION_PURPOSE:
+        raise ValueError(f"vehicle {vehicle!r}: one of {sorted(OBSERVATION_PURPOSE)}")
+    if int(n) != n or not 1 <= int(n) <= 8:
+        raise ValueError("n must be an integer in 1..8")
+    return _ih4_at(seed, ego, step, OBSERVATION_PURPOSE[vehicle], n)
 
 
 def inverse_cdf(p, u):

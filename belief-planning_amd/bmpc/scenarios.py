@@ -524,3 +524,53 @@ def disturbed_quadruped_population(B, steps, sigma_ego=None, sigma_obs=None, dis
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
     _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
     return _closed_loop(pl, scene0, steps, record, device)
+
+
+def _attach_observation(pl, sigma_x, sigma_z, observation_seed, ego_base):
+    """The observation noise of an observed_*_population call (BatchPlan.set_observation); both sigmas
+    None leaves the controller on the true states."""
+    if sigma_x is None and sigma_z is None:
+        return None
+    pl.set_observation(sigma_x, sigma_z, seed=observation_seed, ego_base=ego_base)
+    return pl.observation
+
+
+def observed_overtake_population(B, steps, sigma_x=None, sigma_z=None, observation_seed=0, sigma_ego=None,
+                                 sigma_obs=None, disturbance_seed=0, seed=0, device=0, record=False, obstacle=None,
+                                 obstacle_seed=0, hold=1, ego_base=0, population=None, desc=None):
+    """disturbed_overtake_population with a controller that only measures the scene: the solve of step t
+    is handed x + sigma_x * xi and z + sigma_z * xi, xi = bmpc.rng.observation(observation_seed, global
+    ego, t, vehicle, 4) a unit-variance bounded variate per component (BatchPlan.set_observation).
+    sigma_x / sigma_z: standard deviations of the observed (X, Y, v, psi) of the ego / the obstacle,
+    None: zeros; the suggested use is sigma_x=None, a localised ego that perceives others with noise.
+    The scene, its statistics, x_ref and the record keep the true states; what a solve saw is
+    row + sigma * bmpc.rng.observation(...).  The other arguments are disturbed_overtake_population's,
+    so the sampler, the disturbance and the observation combine; with all four sigmas None it is that
+    entry."""
+    pl, scene0 = _seeded_plan("overtake", B, seed, device, ego_base, population, desc)
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    _attach_observation(pl, sigma_x, sigma_z, observation_seed, ego_base)
+    return _closed_loop(pl, scene0, steps, record, device)
+
+
+def observed_merge_population(B, steps, sigma_x=None, sigma_z=None, observation_seed=0, sigma_ego=None, sigma_obs=None,
+                              disturbance_seed=0, seed=0, device=0, record=False, ego_base=0, population=None):
+    """disturbed_merge_population under observation noise (observed_overtake_population's observation
+    arguments); S and bx stay those of the ego's true state."""
+    pl, scene0 = _seeded_plan("merge", B, seed, device, ego_base, population)
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    _attach_observation(pl, sigma_x, sigma_z, observation_seed, ego_base)
+    return _closed_loop(pl, scene0, steps, record, device)
+
+
+def observed_quadruped_population(B, steps, sigma_x=None, sigma_z=None, observation_seed=0, sigma_ego=None,
+                                  sigma_obs=None, disturbance_seed=0, seed=0, device=0, record=False, obstacle=None,
+                                  obstacle_seed=0, hold=1, ego_base=0, population=None, desc=None):
+    """disturbed_quadruped_population under observation noise: observed_overtake_population's
+    arguments, the sigmas those of the observed (x, y, psi)."""
+    pl, scene0 = _seeded_plan("quadruped", B, seed, device, ego_base, population, desc)
+    _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
+    _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
+    _attach_observation(pl, sigma_x, sigma_z, observation_seed, ego_base)
+    return _closed_loop(pl, scene0, steps, record, device)

@@ -408,27 +408,30 @@ __device__ __attribute__((noinline)) IpmResult loop_ipm(const X ex, const Plan& 
 // argument like env -- two argument registers; the sampled rule lives in here, on lane 0, under a
 // branch on its mode, so the solve's register budget never sees it.  e: the wave's ego.  prop: the
 // plan's device block of scene options (bmpc_env.h SceneOptions: its obstacle proposal,
-// bmpc_set_obstacle_proposal, then its disturbance, bmpc_set_disturbance) or null -- one pointer; the
-// proposal is read by the weighted modes only, the disturbance's law once per step.)
+// bmpc_set_obstacle_proposal, then its disturbance, bmpc_set_disturbance, then its observation model,
+// bmpc_set_observation) or null -- one pointer; the proposal is read by the weighted modes only, the
+// disturbance's and the observation's law once per step.)
 __device__ __attribute__((noinline)) void loop_env_step(const bmpc_env_desc& env, double dt, int N, int m, int t,
                                                         double* st, bmpc_policy* pol, const double* up, double* x,
                                                         double* z, double* xr, double Jv, int status, int iters,
                                                         double* stats, const bmpc_obstacle_sampling& smp,
                                                         const double* mc, int e, const SceneOptions* opt) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, true, stats);
-  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, scene_prop(opt), scene_dist(opt));
+  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, scene_prop(opt), scene_dist(opt),
+               scene_obs(opt));
 }
 
 // One merge-scene step of one ego into its slab (k_env_merge and the merge k_loop): the scene
 // function writes S and bx straight into the ego's transform slots and marks them set (S on),
 // which is all bmpc_set_transform would have scattered there.  opt: the plan's scene options or null
-// (the merge scene reads the disturbance only: its obstacle never chooses), e: the ego's index.
+// (the merge scene reads the disturbance and the observation model: its obstacle never chooses), e: the
+// ego's index.
 __device__ __forceinline__ void merge_env_step_slab(const bmpc_merge_env_desc& env, const MergeRef& R, const Plan& P,
                                                     const Layout& L, int t, double* st, double* ws, const double* up,
                                                     double* x, double* z, double* xr, const SceneOptions* opt, int e) {
   double* xf = ws + L.xform;
   merge_env_step_ego(env, R, P.desc.bx, P.nFx, P.desc.dt, t, st, up, x, z, xr, xf + XF_S, xf + XF_BX,
-                     scene_dist(opt), e);
+                     scene_dist(opt), e, scene_obs(opt));
   xf[XF_SON] = 1.0;
   xf[XF_BXSET] = 1.0;
 }
@@ -455,7 +458,7 @@ __device__ __attribute__((noinline)) void loop_quad_env_step(const bmpc_quad_env
                                                              const SceneOptions* opt) {
   if (t > 0 && stats) env_accumulate(st, Jv, status, iters, false, stats);
   quad_env_step_ego(env, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol, up, x, z, xr, &smp, e, scene_prop(opt),
-                    scene_dist(opt));
+                    scene_dist(opt), scene_obs(opt));
 }
 
 // Ego e's row r of the closed loops' recorder (bmpc_record.h), by the 64 lanes of one wave: the
@@ -501,7 +504,8 @@ __device__ __attribute__((noinline)) void loop_record_wide(double* upred, double
 // out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
 // ego's transform slots, the quadruped scene neither.  The overtake and the quadruped scene carry the
 // plan's obstacle sampler (mode 0: none); the merge scene's obstacle never chooses.  All three carry
-// a pointer to the plan's scene options (null: none): the proposal and the disturbance.  kQp: the step's
+// a pointer to the plan's scene options (null: none): the proposal, the disturbance and the observation
+// model.  kQp: the step's
 // solve is the OSQP-class controllers' solve_ego_qp (k_qp's) instead of the CVaR IPM.  kInlineIpm: the solve inlined into
 // the kernel as k_ipm / k_qp have it (the tree and scene steps stay calls) instead of a call of
 // its own -- as a callee the IPM's frame grows from k_ipm's ~590 to ~1,490 bytes per lane (merge

@@ -124,13 +124,16 @@ BMPC_HD bool env_samples(const bmpc_obstacle_sampling* smp) { return smp && smp-
 // What a plan has attached to its scenes beyond the sampler, as one device block behind one pointer
 // (null: nothing attached): the obstacle proposal (bmpc_set_obstacle_proposal; read only in the
 // sampler modes that need one, which the host admits only while one is attached) followed by the
-// actuation disturbance (bmpc_set_disturbance; law BMPC_DISTURB_NONE while none is attached).
+// actuation disturbance (bmpc_set_disturbance; law BMPC_DISTURB_NONE while none is attached) and the
+// observation model (bmpc_set_observation; law BMPC_OBSERVE_NONE while none is attached).
 struct SceneOptions {
   bmpc_obstacle_proposal prop;
   bmpc_disturbance dist;
+  bmpc_observation obs;
 };
 BMPC_HD const bmpc_obstacle_proposal* scene_prop(const SceneOptions* o) { return o ? &o->prop : nullptr; }
 BMPC_HD const bmpc_disturbance* scene_dist(const SceneOptions* o) { return o ? &o->dist : nullptr; }
+BMPC_HD const bmpc_observation* scene_obs(const SceneOptions* o) { return o ? &o->obs : nullptr; }
 
 // One scene step of one ego (see the header comment).  st: ENV_STRIDE doubles; pol: the
 // ego's m model policies (the lane-change target is re-targeted in place, update_backup);
@@ -139,13 +142,15 @@ BMPC_HD const bmpc_disturbance* scene_dist(const SceneOptions* o) { return o ? &
 // reference's argmax rule), with mc, the plan's model constants, and e, the ego's index in the plan;
 // prop: the plan's obstacle proposal (read in modes BMPC_OBS_SAMPLE_TILTED and BMPC_OBS_SCRIPT only);
 // dist: the plan's actuation disturbance or null (bmpc_set_disturbance: the inputs post(t-1) applies,
-// rng_disturb_input; the row's ENV_UOBS keeps the nominal input).
+// rng_disturb_input; the row's ENV_UOBS keeps the nominal input); obs: the plan's observation model or
+// null (bmpc_set_observation: x_out and z_out only, rng_observe_state at step t; the row, the choice,
+// the bookkeeping and xref_out stay on the true states).
 BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t, double* st,
                           bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
                           double* xref_out, const bmpc_obstacle_sampling* smp = nullptr,
                           const double* mc = nullptr, long long e = 0,
                           const bmpc_obstacle_proposal* prop = nullptr,
-                          const bmpc_disturbance* dist = nullptr) {
+                          const bmpc_disturbance* dist = nullptr, const bmpc_observation* obs = nullptr) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
@@ -224,8 +229,8 @@ BMPC_HD void env_step_ego(const bmpc_env_desc& E, double dt, int N, int m, int t
   // x_ref rule (:153-167)
   const double Ydes = x[0] < z[0] ? 1.8 + st[ENV_LANE0] * 3.6 : z[1];
   const double vdes = (fabs(x[1] - Ydes) < 1.0 && x[0] > z[0] + 3.0) ? E.v0 : z[2] + (z[0] + 1.5 - x[0]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x_out[i] = x[i], z_out[i] = z[i];
+  rng_observe_state(obs, true, e, t, 4, x, x_out);
+  rng_observe_state(obs, false, e, t, 4, z, z_out);
   xref_out[0] = 0.0;
   xref_out[1] = Ydes;
   xref_out[2] = vdes;

@@ -35,11 +35,13 @@ struct MergeRef {
 // t == 0); x_out, z_out, xref_out: the next solve's inputs; S_out [4][4] and bx_out [nbx]: the
 // solve's state transformation and state bound (nbx >= 4 on the ramp's rule).  dist: the plan's
 // actuation disturbance or null (bmpc_set_disturbance, as in env_step_ego), with e, the ego's index
-// in the plan.
+// in the plan; obs: the plan's observation model or null (bmpc_set_observation: x_out and z_out only;
+// xref_out, S_out and bx_out are those of the true state).
 BMPC_HD void merge_env_step_ego(const bmpc_merge_env_desc& E, const MergeRef& R, const double* bx_plan, int nbx,
                                 double dt, int t, double* st, const double* u0, double* x_out, double* z_out,
                                 double* xref_out, double* S_out, double* bx_out,
-                                const bmpc_disturbance* dist = nullptr, long long e = 0) {
+                                const bmpc_disturbance* dist = nullptr, long long e = 0,
+                                const bmpc_observation* obs = nullptr) {
   double* x = st + ENV_X;
   double* z = st + ENV_Z;
   if (t > 0) {   // post(t-1): vehicle.step of ego and obstacle
@@ -83,8 +85,8 @@ BMPC_HD void merge_env_step_ego(const bmpc_merge_env_desc& E, const MergeRef& R,
     bx_out[2] = psi0 + E.psimax;
     bx_out[3] = -psi0 + E.psimax;
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x_out[i] = x[i], z_out[i] = z[i];
+  rng_observe_state(obs, true, e, t, 4, x, x_out);
+  rng_observe_state(obs, false, e, t, 4, z, z_out);
   st[ENV_STEPS] += 1.0;
 }
 

@@ -43,12 +43,13 @@ BMPC_HD double quad_env_robot_col(const double* mc, double a0, double a1, double
 // t == 0); x_out, z_out, xref_out: the next solve's inputs (3 doubles each).  smp: the plan's
 // obstacle sampler or null (null and mode BMPC_OBS_ARGMAX are the reference's rule); e: the ego's
 // index in the plan; prop: the plan's obstacle proposal (the weighted modes, bmpc_env.h); dist: the
-// plan's actuation disturbance or null (bmpc_set_disturbance, as in env_step_ego).
+// plan's actuation disturbance or null (bmpc_set_disturbance, as in env_step_ego); obs: the plan's
+// observation model or null (bmpc_set_observation: x_out and z_out only; xref_out is the true state's).
 BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, double dt, int N, int m, int t,
                                double* st, const bmpc_policy* pol, const double* u0, double* x_out, double* z_out,
                                double* xref_out, const bmpc_obstacle_sampling* smp = nullptr, long long e = 0,
                                const bmpc_obstacle_proposal* prop = nullptr,
-                               const bmpc_disturbance* dist = nullptr) {
+                               const bmpc_disturbance* dist = nullptr, const bmpc_observation* obs = nullptr) {
   double* x = st + QENV_X;
   double* z = st + QENV_Z;
   if (t > 0) {   // post(t-1): robot.step of ego and obstacle
@@ -104,8 +105,8 @@ BMPC_HD void quad_env_step_ego(const bmpc_quad_env_desc& E, const double* mc, do
     for (int i = 0; i < 64 && psi - xd[2] > pi; ++i) psi -= 2.0 * pi;
     for (int i = 0; i < 64 && psi - xd[2] < -pi; ++i) psi += 2.0 * pi;
   }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) x_out[i] = x[i], z_out[i] = z[i];
+  rng_observe_state(obs, true, e, t, 3, x, x_out);
+  rng_observe_state(obs, false, e, t, 3, z, z_out);
   xref_out[0] = x[0] + d0;
   xref_out[1] = x[1] + d1;
   xref_out[2] = psi;

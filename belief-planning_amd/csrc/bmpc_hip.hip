@@ -39,7 +39,7 @@ static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, s
 // one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve.  smp: the plan's
 // obstacle sampler (mode 0: the argmax rule), mc: the plan's model constants on the device, opt: the
 // plan's device block of scene options (null: none; bmpc_env.h SceneOptions -- the obstacle proposal,
-// read by the weighted modes only, and the actuation disturbance)
+// read by the weighted modes only, the actuation disturbance and the observation model)
 __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, int t, int batch, double* scene,
                       bmpc_policy* pol, const double* upred, const double* J, const int32_t* status,
                       const int32_t* iters, int cvar, double* x, double* z, double* xref, double* stats,
@@ -51,7 +51,7 @@ __global__ void k_env(bmpc_env_desc E, double dt, int N, int m, int U, int d, in
     env_accumulate(st, J[e], status[e], iters[e], cvar != 0, stats + (size_t)e * ENVS_STRIDE);
   env_step_ego(E, dt, N, m, t, st, pol + (size_t)e * m, upred ? upred + (size_t)e * U * d : nullptr,
                x + (size_t)e * 4, z + (size_t)e * 4, xref + (size_t)e * 4, &smp, mc, e, scene_prop(opt),
-               scene_dist(opt));
+               scene_dist(opt), scene_obs(opt));
 }
 
 // one thread per ego: the merge scene step (bmpc_env_merge.h) around the solve; S, bx and their
@@ -85,7 +85,7 @@ __global__ void k_env_quad(const Bundle* __restrict__ B, bmpc_quad_env_desc E, i
     env_accumulate(st, J[e], status[e], iters[e], false, stats + (size_t)e * ENVS_STRIDE);
   quad_env_step_ego(E, P.desc.mc, P.desc.dt, P.N, P.m, t, st, pol + (size_t)e * P.m,
                     upred ? upred + (size_t)e * P.U * P.d : nullptr, x + (size_t)e * 3, z + (size_t)e * 3,
-                    xref + (size_t)e * 3, &smp, e, scene_prop(opt), scene_dist(opt));
+                    xref + (size_t)e * 3, &smp, e, scene_prop(opt), scene_dist(opt), scene_obs(opt));
 }
 
 // One wave per ego: step t's row of the closed loops' recorder after the per-step launches (run_loop)
@@ -543,14 +543,16 @@ struct bmpc_plan {
   int n_mref = 0;   // 0: no merge scene set
   bmpc_loop_record rec = {};   // the closed loops' recorder (bmpc_set_loop_record; capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the scenes' obstacle sampler (bmpc_set_obstacle_sampling; mode 0: none)
-  // the obstacle proposal (bmpc_set_obstacle_proposal) and the actuation disturbance
-  // (bmpc_set_disturbance): the host copies, and the device block of both that the scene kernels read
-  // through one pointer (allocated at the first attach of either; has_prop / has_dist false: none
-  // attached -- the block's disturbance then has law BMPC_DISTURB_NONE)
+  // the obstacle proposal (bmpc_set_obstacle_proposal), the actuation disturbance (bmpc_set_disturbance)
+  // and the observation model (bmpc_set_observation): the host copies, and the device block of the
+  // three that the scene kernels read through one pointer (allocated at the first attach of any;
+  // has_prop / has_dist / has_obs false: none attached -- the block's disturbance / observation then
+  // has law NONE)
   bmpc_obstacle_proposal prop = {};
   bmpc_disturbance dist = {};
+  bmpc_observation obs = {};
   SceneOptions* d_opt = nullptr;
-  bool has_prop = false, has_dist = false;
+  bool has_prop = false, has_dist = false, has_obs = false;
   uint64_t* d_rs = nullptr;   // bmpc_resample_device's scans (2 * batch uint64, allocated at the first call)
   PhasedPlan ph;   // (empty but in tools-only builds)
 };
@@ -570,20 +572,22 @@ static int drain(bmpc_plan* pl) {
 }
 
 // the options pointer the scene kernels get: the plan's device block, or null when neither a proposal
-// nor a disturbance is attached
+// nor a disturbance nor an observation model is attached
 static const SceneOptions* scene_options(const bmpc_plan* pl) {
-  return pl->has_prop || pl->has_dist ? pl->d_opt : nullptr;
+  return pl->has_prop || pl->has_dist || pl->has_obs ? pl->d_opt : nullptr;
 }
 
 // the plan's host copies into its device block, allocated at the first call, after draining the
 // plan's streams: no scene step in flight reads the old block
-static int upload_scene_options(bmpc_plan* pl, const bmpc_obstacle_proposal& prop, const bmpc_disturbance& dist) {
+static int upload_scene_options(bmpc_plan* pl, const bmpc_obstacle_proposal& prop, const bmpc_disturbance& dist,
+                                const bmpc_observation& obs) {
   HIPCHECK(hipSetDevice(pl->ctx->device));
   if (const int rc = drain(pl)) return rc;
   if (!pl->d_opt) HIPCHECK(hipMalloc(&pl->d_opt, sizeof(SceneOptions)));
   SceneOptions h;
   h.prop = prop;
   h.dist = dist;
+  h.obs = obs;
   HIPCHECK(hipMemcpy(pl->d_opt, &h, sizeof(h), hipMemcpyHostToDevice));
   return 0;
 }
@@ -1022,8 +1026,8 @@ extern "C++" {
 // launches k_loop_record after each solve whose step lies in the window.  The plan's obstacle sampler
 // (bmpc_set_obstacle_sampling) reaches both paths: k_loop's scene argument carries it, and `step` is
 // the single-step entry point, which passes it to k_env / k_env_quad; the pointer to the plan's scene
-// options -- its obstacle proposal (bmpc_set_obstacle_proposal) and its disturbance
-// (bmpc_set_disturbance) -- travels beside it on both, to the merge scene too.
+// options -- its obstacle proposal (bmpc_set_obstacle_proposal), its disturbance (bmpc_set_disturbance)
+// and its observation model (bmpc_set_observation) -- travels beside it on both, to the merge scene too.
 template <class Step, class Fused>
 static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nsteps, double* d_scene, double* d_upred,
                     double* d_x, double* d_z, double* d_xref, double* d_J, int32_t* d_status, int32_t* d_iters,
@@ -1313,7 +1317,7 @@ int bmpc_set_obstacle_proposal(bmpc_plan* pl, const bmpc_obstacle_proposal* q) {
   bmpc_obstacle_proposal h = *q;
   for (int j = P.m; j < BMPC_MAX_M; ++j) h.tilt[j] = 1.0;   // (never read)
   if (h.script_epochs == 0) h.script = nullptr;
-  if (const int rc = upload_scene_options(pl, h, pl->dist)) return rc;
+  if (const int rc = upload_scene_options(pl, h, pl->dist, pl->obs)) return rc;
   pl->prop = h;
   pl->has_prop = true;
   return 0;
@@ -1337,10 +1341,10 @@ int bmpc_set_disturbance(bmpc_plan* pl, const bmpc_disturbance* d) {
   if (!pl) return fail(-22, "null argument");
   const Plan& P = pl->hp.plan;
   if (!d) {
-    // (the block stays allocated: a loop in flight may still read it; where an attached proposal keeps
-    // its pointer in use by the launches to come, the block's law is cleared)
-    if (pl->has_dist && pl->has_prop)
-      if (const int rc = upload_scene_options(pl, pl->prop, bmpc_disturbance{})) return rc;
+    // (the block stays allocated: a loop in flight may still read it; where an attached proposal or
+    // observation model keeps its pointer in use by the launches to come, the block's law is cleared)
+    if (pl->has_dist && (pl->has_prop || pl->has_obs))
+      if (const int rc = upload_scene_options(pl, pl->prop, bmpc_disturbance{}, pl->obs)) return rc;
     pl->has_dist = false;
     pl->dist = bmpc_disturbance{};
     return 0;
@@ -1360,9 +1364,41 @@ int bmpc_set_disturbance(bmpc_plan* pl, const bmpc_disturbance* d) {
   if (const std::string e = check_scene_plan(P); !e.empty()) return fail(-22, "bmpc_set_disturbance: " + e);
   bmpc_disturbance h = *d;
   h.reserved = 0;
-  if (const int rc = upload_scene_options(pl, pl->prop, h)) return rc;
+  if (const int rc = upload_scene_options(pl, pl->prop, h, pl->obs)) return rc;
   pl->dist = h;
   pl->has_dist = true;
+  return 0;
+}
+
+int bmpc_set_observation(bmpc_plan* pl, const bmpc_observation* o) {
+  if (!pl) return fail(-22, "null argument");
+  const Plan& P = pl->hp.plan;
+  if (!o) {
+    // (as bmpc_set_disturbance detaches: the law is cleared where another option keeps the pointer in use)
+    if (pl->has_obs && (pl->has_prop || pl->has_dist))
+      if (const int rc = upload_scene_options(pl, pl->prop, pl->dist, bmpc_observation{})) return rc;
+    pl->has_obs = false;
+    pl->obs = bmpc_observation{};
+    return 0;
+  }
+  if (o->law != BMPC_OBSERVE_NONE && o->law != BMPC_OBSERVE_IH4)
+    return fail(-22, "bmpc_set_observation: unknown law (BMPC_OBSERVE_NONE or BMPC_OBSERVE_IH4)");
+  if (o->ego_base < 0) return fail(-22, "bmpc_set_observation: ego_base must not be negative");
+  for (int v = 0; v < 2; ++v)
+    for (int c = 0; c < BMPC_MAX_N; ++c) {
+      const double sg = v == 0 ? o->sigma_x[c] : o->sigma_z[c];
+      const std::string name = std::string(v == 0 ? "sigma_x[" : "sigma_z[") + std::to_string(c) + "]";
+      if (!(std::isfinite(sg) && sg >= 0.0)) return fail(-22, "bmpc_set_observation: " + name + " must be finite and >= 0");
+      if (c >= P.n && sg != 0.0)
+        return fail(-22, "bmpc_set_observation: " + name + " must be 0: the plan's states have " + std::to_string(P.n) +
+                             " components");
+    }
+  if (const std::string e = check_scene_plan(P); !e.empty()) return fail(-22, "bmpc_set_observation: " + e);
+  bmpc_observation h = *o;
+  h.reserved = 0;
+  if (const int rc = upload_scene_options(pl, pl->prop, pl->dist, h)) return rc;
+  pl->obs = h;
+  pl->has_obs = true;
   return 0;
 }
 

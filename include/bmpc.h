@@ -38,6 +38,8 @@
  *                         per ego and epoch, with a running log-weight in the scene row)
  *   bmpc_set_disturbance         (an extension: an actuation disturbance on both vehicles' inputs
  *                         in the scenes' Euler steps, drawn per step)
+ *   bmpc_set_observation         (an extension: observation noise on the ego and obstacle states the
+ *                         scenes hand to the next solve, drawn per step; the scenes keep the truth)
  *   bmpc_population_ancestors / bmpc_gather_egos / bmpc_resample_device   (an extension: resampling a
  *                         weighted population between loop segments, on the device)
  *
@@ -613,6 +615,57 @@ static_assert(sizeof(bmpc_disturbance) == 24 + 16 * BMPC_MAX_D && offsetof(bmpc_
  * message for an unknown law, ego_base < 0, a negative or non-finite sigma, a non-zero sigma at a
  * component >= d, and a plan that none of the three scene entries accepts. */
 int bmpc_set_disturbance(bmpc_plan* plan, const bmpc_disturbance* d);
+
+/* Observation noise in the device closed loops: a perception model between the scene and the
+ * controller.  Without it every scene step hands the solve the true ego state x and the true obstacle
+ * state z, from which the tree derives the branch probabilities, the obstacle rollouts and the
+ * collision rows.  An extension: the reference's controllers see the scene exactly.
+ *
+ * The law BMPC_OBSERVE_IH4 is the disturbance's variate xi (above; csrc/bmpc_rng.h rng_ih4, restated
+ * by bmpc/rng.py) at the counter {lo32(g), hi32(g), t, purpose} with key = seed, g = ego_base + e the
+ * ego's global index, t the closed-loop step whose solve sees the observation, and
+ * purpose = 16 + c for component c of the obstacle's state, 24 + c for the ego's (c < BMPC_MAX_N).
+ *
+ * While it is attached each of the three scene steps changes only its last two outputs, the vectors
+ * the next solve reads:
+ *   x_out[c] = x[c] + sigma_x[c] * xi(g, t, 24 + c)        c < n
+ *   z_out[c] = z[c] + sigma_z[c] * xi(g, t, 16 + c)
+ * the product rounded before it is added; a component with sigma == 0 makes no draw and passes
+ * through to the bit.  Everything else in the step stays on the truth: the Euler steps and the
+ * collision rule, the merged flag, the lane bookkeeping and the lane-change re-targeting, the
+ * obstacle's choice in every sampler mode with its input and BMPC_ENV_LOGW, the statistics, x_ref and
+ * the merge scene's S and bx.  The scene row and the recorder keep the true states; what the solve saw
+ * is row + sigma * xi, reproducible on the host.  The loop entries' d_x / d_z hold the observed
+ * vectors.  There is no per-ego state: a draw is addressed by slot, so clones made by
+ * bmpc_gather_egos diverge by themselves. */
+enum { BMPC_OBSERVE_NONE = 0, BMPC_OBSERVE_IH4 = 1 };
+typedef struct {
+  int32_t  law, reserved;          /* BMPC_OBSERVE_*; reserved is ignored                 */
+  uint64_t seed;
+  int64_t  ego_base;               /* >= 0, as in bmpc_obstacle_sampling                  */
+  double   sigma_x[BMPC_MAX_N];    /* the ego's own state: >= 0 and finite; 0 at the components >= n */
+  double   sigma_z[BMPC_MAX_N];    /* the obstacle's state                                */
+} bmpc_observation;
+#ifdef __cplusplus
+static_assert(sizeof(bmpc_observation) == 24 + 16 * BMPC_MAX_N && offsetof(bmpc_observation, law) == 0 &&
+                  offsetof(bmpc_observation, seed) == 8 && offsetof(bmpc_observation, ego_base) == 16 &&
+                  offsetof(bmpc_observation, sigma_x) == 24 &&
+                  offsetof(bmpc_observation, sigma_z) == 24 + 8 * BMPC_MAX_N,
+              "bmpc_observation is 152 bytes: law 0, seed 8, ego_base 16, sigma_x 24, sigma_z 88");
+#endif
+
+/* Attach (a copy of *o: one on the host and one on the device, behind the proposal's and the
+ * disturbance's in the block the scene kernels read through one pointer) or detach (o == NULL) the
+ * plan's observation model; bmpc_set_disturbance's contract.  Re-attaching waits for the plan's
+ * streams before the device copy is overwritten; detaching leaves the device copy allocated (and,
+ * where an attached proposal or disturbance keeps the pointer in use, clears its law the same way).
+ * Obeyed by bmpc_loop_device, bmpc_merge_loop_device and bmpc_quad_loop_device on either launch path
+ * and by the single-step bmpc_env_step, bmpc_merge_env_step and bmpc_quad_env_step, so a manual loop
+ * gets the same bits.  With law BMPC_OBSERVE_NONE, all sigmas zero or nothing attached every path
+ * computes the bits it computed without this entry.  -22 with a message for an unknown law,
+ * ego_base < 0, a negative or non-finite sigma, a non-zero sigma at a component >= n, and a plan that
+ * none of the three scene entries accepts. */
+int bmpc_set_observation(bmpc_plan* plan, const bmpc_observation* o);
 
 /* Resampling a weighted population between loop segments (sequential Monte Carlo / particle
  * splitting): egos of large weight are cloned into the slots of egos of negligible weight and every

@@ -38,9 +38,10 @@ SIGMAS = {"overtake": ((0.3, 0.01), (0.5, 0.02)), "merge": ((0.3, 0.01), (0.5, 0
           "quadruped": ((0.02, 0.01, 0.05), (0.02, 0.01, 0.05))}
 
 
-def run(shape, egos, steps, warmup, seed, sigmas=None):
+def run(shape, egos, steps, warmup, seed, sigmas=None, attach=None):
     """One repetition: a fresh plan of the shape's seeded population, `warmup` steps, then `steps` timed
-    ones.  sigmas: None or (sigma_ego, sigma_obs) attached with seed `seed`."""
+    ones.  sigmas: None or (sigma_ego, sigma_obs) attached with seed `seed`; attach: None or a function
+    of the plan that attaches another scene option (tools/observation_measure.py)."""
     import torch
     dev = torch.device("cuda", 0)
     f64 = dict(dtype=torch.float64, device=dev)
@@ -67,6 +68,8 @@ def run(shape, egos, steps, warmup, seed, sigmas=None):
         scene0 = scenarios._overtake_scene(x, z)
     if sigmas is not None:
         pl.set_disturbance(*sigmas, seed=seed)
+    if attach is not None:
+        attach(pl)
     n, d = pl.desc.n, pl.desc.d
     scene = torch.tensor(scene0, **f64)
     up = torch.zeros((egos, pl.U, d), **f64)
