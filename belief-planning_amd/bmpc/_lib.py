@@ -91,6 +91,18 @@ def build(force: bool = False, verbose: bool = False, profile: bool = False) -> 
     return out
 
 
+def build_variant(tag: str, flags, force: bool = False) -> str:
+    """``libbmpc_<tag>.so``: the same sources with extra -D flags (an A/B library, loaded through
+    BMPC_LIBRARY); its stamp is the sources' hash, so an up-to-date one is kept unless forced."""
+    global SO_PATH
+    keep_path, keep_flags = SO_PATH, EXTRA_FLAGS[:]
+    SO_PATH, EXTRA_FLAGS[:] = os.path.join(PKG_DIR, f"libbmpc_{tag}.so"), list(flags)
+    try:
+        return build(force=force)
+    finally:
+        SO_PATH, EXTRA_FLAGS[:] = keep_path, keep_flags
+
+
 _LIB = None
 
 _SIGS = {

@@ -28,6 +28,17 @@
 #else
 #define BMPC_FN_CALLS
 #endif
+// BMPC_ITER_RECORD: the IPM loop's wave-uniform iteration state (tau, kappa, the residual norms'
+// scales, the best iterate's figures, the step quantities) in one per-ego record of doubles behind
+// an accessor (bmpc_ipm.h, IterRec) instead of in locals held across the phase calls.  On the
+// one-wave device executor the record is in the wave's LDS (Plan::lds_it) and every pass fetches
+// the scalars it uses as SGPR operands just before its lane loop; on the host build it is a local
+// struct; the multi-wave small-batch executor keeps the locals (kIterRecord = false, bmpc_dev.h).
+// 0: the locals everywhere.  Same operations on the same values either way.
+#ifndef BMPC_ITER_RECORD
+#define BMPC_ITER_RECORD 1
+#endif
+#define BMPC_ITER_LDS 32   // doubles of LDS the record takes (IterRec's slots, rounded up)
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define BMPC_HD __host__ __device__ __forceinline__
@@ -157,7 +168,8 @@ struct Plan {
   int lds_w, lds_wu, lds_fx, lds_fu, nconst;
   int nlds_lean;            // LDS doubles when the coupling system lives in the slab (Layout::coup)
   int lds_scr, nscr;       // tree-solve LDS scratch (slack terms of the pre-pass; 0 = none)
-  int cgrp;   // lanes per cone group (power of two, cgrp * ceil(ncones / ngrp) covers all cones)
+  int lds_it;              // the IPM's iteration record (BMPC_ITER_LDS doubles; before lds_piv: lean launches have it)
+  int cgrp;  // lanes per cone group (power of two, cgrp * ceil(ncones / ngrp) covers all cones)
   int maxq;   // largest cone dimension (fused cone passes hold a cone's rows in registers when
               // maxq <= X::kConeRegRows * cgrp)
   double W1[BMPC_MAX_N * BMPC_MAX_N];   // sqrtm(Q) / chol(Q)'  (MPC_branch.py:1628-1631)

@@ -80,6 +80,14 @@ struct DevExecT {
   // a wave-uniform flag as a scalar: branches on it (and the calls they guard) run with the
   // full exec mask instead of an exec mask derived from a VGPR the compiler cannot prove uniform
   __device__ bool uniform(bool b) const { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+  // a wave-uniform double as a scalar pair: an SGPR operand of the lane loops that use it
+  __device__ double uniform(double v) const {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
+  }
+  // the IPM's iteration record in this wave's LDS (bmpc_ipm.h, IterRec; Plan::lds_it): one wave per
+  // workgroup, so a slot written by every lane is read back by every lane without a barrier
+  static constexpr bool kIterLds = BMPC_ITER_RECORD != 0;
   __device__ double sum(double v) const { return wave_reduce<0, kDppWave>(v); }
   __device__ double max(double v) const { return wave_reduce<1, kDppWave>(v); }
   __device__ double min(double v) const { return wave_reduce<2, kDppWave>(v); }
@@ -125,6 +133,7 @@ struct DevBlockExecT {
   static constexpr int kConeRegRows = NW == 4 ? 4 : 8;
   static constexpr int kConeBatch = NW == 4 ? 2 : 4;
   static constexpr int kRedMax = 16;
+  static constexpr bool kIterRecord = false;   // the IPM loop with its state in locals (bmpc_ipm.h, ipm_solve)
   __device__ double tsum(double v) const {
     v += dpp_d<0xB1>(v);
     v += dpp_d<0x4E>(v);

@@ -3865,10 +3865,539 @@ struct IpmResult {
 };
 
 // ------------------------------------------------------------------------------------
+// The IPM loop's iteration record (BMPC_ITER_RECORD): its wave-uniform state as named slots of
+// doubles.  Executors with kIterLds (the one-wave kernels) keep it in the wave's LDS at
+// Plan::lds_it: a slot is stored by every lane (the same value) and loaded as a scalar
+// (ex.uniform: an SGPR pair), so nothing of it is held in VGPRs -- and spilled -- across the
+// phase calls, and a lane loop takes it as a scalar operand.  The accesses are volatile: a value
+// forwarded from its store to a later load would be back in a VGPR pair for that stretch.  The
+// host build keeps a local struct behind the same accessor; the multi-wave small-batch kernel
+// runs the loop with locals (ipm_solve below), so no barrier is added anywhere.
+// ------------------------------------------------------------------------------------
+enum {
+  IT_TAU = 0, IT_KAP, IT_RESX0, IT_RESY0, IT_RESZ0,
+  IT_BEST, IT_BEST_TAU, IT_BEST_IT,                                            // the best iterate's score, tau, iteration
+  IT_BS_PRES, IT_BS_DRES, IT_BS_RELGAP, IT_BS_GAP, IT_BS_PCOST, IT_BS_OK_CX,   // ... and its exit figures
+  IT_RT, IT_MU, IT_KT,                                                         // of the residual section (KT = kap tau)
+  IT_DEN, IT_DTAU_A, IT_DKAP_A, IT_SIGMA, IT_ETA1, IT_SMU, IT_DTAU, IT_DKAP,   // of the Newton step (SMU = sigma mu)
+  IT_COUNT
+};
+static_assert(IT_COUNT <= BMPC_ITER_LDS, "the iteration record's LDS area (bmpc_core.h)");
+template <class X, class = void>
+struct iter_lds { static constexpr bool value = false; };
+template <class X>
+struct iter_lds<X, decltype((void)X::kIterLds)> { static constexpr bool value = X::kIterLds; };
+
+// a pointer the optimiser takes as new (device builds): loads through it are not hoisted or merged with earlier ones
+template <class T>
+BMPC_HD T* opaque_ptr(T* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  p = uniform_ptr(p);   // (an out-of-line caller's argument arrives in VGPRs)
+  asm volatile("" : "+s"(p));
+#endif
+  return p;
+}
+
+// a wave-uniform double as a scalar where the executor has the record in LDS (else as it is)
+template <class X>
+BMPC_HD double ex_uniform(const X& ex, double v) {
+  if constexpr (iter_lds<X>::value) return ex.uniform(v);
+  else return v;
+}
+
+template <class X, bool LDS = iter_lds<X>::value>
+struct IterRec {
+  double v[IT_COUNT];
+  BMPC_HD IterRec(const X&, CPlan&) {}
+  BMPC_HD double ld(int k) const { return v[k]; }
+  BMPC_HD void st(int k, double a) { v[k] = a; }
+};
+template <class X>
+struct IterRec<X, true> {
+  const X& ex;
+  volatile ldouble* p;
+  BMPC_HD IterRec(const X& e, CPlan& P) : ex(e), p(e.lds + P.lds_it) {}
+  BMPC_HD double ld(int k) const { return ex.uniform((double)p[k]); }
+  BMPC_HD void st(int k, double a) { p[k] = a; }
+};
+
+// ------------------------------------------------------------------------------------
 // the HSDE interior-point loop (ECOS algorithm; oracle/ecos_ipm.py is its CPU restatement)
 // ------------------------------------------------------------------------------------
+#if BMPC_ITER_RECORD
+// The loop with its state in the iteration record: every pass reads the scalars it uses from the
+// record just before its lane loop, every scalar result goes straight back, and the slab's arrays
+// are addressed as ws + L.<field> where they are used (L is constant memory) instead of through
+// two dozen pointers held across the calls.  The floating-point operations, their operands and
+// their order are those of the text with locals below.
 template <class X, int NX, int NU>
-BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
+BMPC_HD IpmResult ipm_solve_record(const X ex, const Ctx& C) {
+  CPlan& P = *C.P;
+  CLayout& L = *C.L;
+  gdouble* ws = C.ws;
+  const int nv = P.nv, neq = P.neq, nr = P.nrows;
+  IterRec<X> R(ex, P);
+  // the layout as the loop reads it: through a pointer the compiler cannot see through (one-wave
+  // kernels), so a slab offset is a scalar load where it is used and not a register pair hoisted
+  // out of the loop and held -- spilled -- across every call of an iteration
+  auto LL = [&]() -> CLayout& { return *(iter_lds<X>::value ? opaque_ptr(C.L) : C.L); };
+  IpmResult res{EXIT_MAXIT, 0, 0.0};
+  BMPC_PROF(ws, L, PROF_TOTAL);
+  BMPC_TIC(t_init);
+  if (BMPC_EQUIL) equilibrate<X, NX, NU>(ex, C);
+  build_hb<X, NX, NU>(ex, C, ws + L.hvec, ws + L.bvec);
+  // ---- initial point with W = I (of the equilibrated variables) ----------------------------
+  identity_scaling(ex, C);
+  if (!kkt_factor<X, NX, NU>(ex, C, true) || !kkt_coupling<X, NX, NU>(ex, C, 0)) {
+    res.exit_flag = EXIT_NUMERICS;
+    return res;
+  }
+  {
+    gdouble* tA = ws + L.ta;
+    lane_batch<16>(ex, 0, nv, [&](int i) { return 0.0; }, [&](int i, double v) { tA[i] = v; });
+    ex.sync();
+  }
+  kkt_solve_flat<X, NX, NU>(ex, C, ws + L.ta, ws + L.bvec, ws + L.hvec, ws + L.x, ws + L.y2, ws + L.z2,
+                            BMPC_NITREF_INIT);
+  // s = ge bring2cone(-ge z)  (ECOS: s~ = bring2cone(-z~), z~ = ge z, s = ge s~)
+  {
+    const gdouble* gq = ws + L.geq;
+    const gdouble* z2 = ws + L.z2;
+    gdouble* ra = ws + L.ra;
+    lane_batch<16>(ex, 0, nr, [&](int i) { return -(BMPC_EQUIL ? gq[i] : 1.0) * z2[i]; }, [&](int i, double v) { ra[i] = v; });
+    ex.sync();
+  }
+  bring2cone(ex, C, ws + L.ra, ws + L.s);
+  if (BMPC_EQUIL) {
+    const gdouble* gq = ws + L.geq;
+    gdouble* s = ws + L.s;
+    lane_batch<16>(ex, 0, nr, [&](int i) { return gq[i] * s[i]; }, [&](int i, double v) { s[i] = v; });
+    ex.sync();
+  }
+  // -c = -e_J: this solve's right-hand side and the c direction's of every iteration
+  {
+    gdouble* ej = BMPC_IPM_LEAN_PASSES ? ws + L.ej : ws + L.ta;
+    gdouble* ya = ws + L.ya;
+    gdouble* ra = ws + L.ra;
+    lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { ej[i] = v; });
+    lane_batch(ex, 0, neq, [&](int i) { return 0.0; }, [&](int i, double v) { ya[i] = v; });
+    lane_batch<16>(ex, 0, nr, [&](int i) { return 0.0; }, [&](int i, double v) { ra[i] = v; });
+    ex.sync();
+    kkt_solve_flat<X, NX, NU>(ex, C, ej, ya, ra, ws + L.x2, ws + L.y, ws + L.z2, BMPC_NITREF_INIT);
+  }
+  // z = bring2cone(ge z) / ge
+  if (BMPC_EQUIL) {
+    const gdouble* gq = ws + L.geq;
+    gdouble* z2 = ws + L.z2;
+    lane_batch<16>(ex, 0, nr, [&](int i) { return gq[i] * z2[i]; }, [&](int i, double v) { z2[i] = v; });
+    ex.sync();
+  }
+  bring2cone(ex, C, ws + L.z2, ws + L.z);
+  if (BMPC_EQUIL) {
+    const gdouble* gq = ws + L.geq;
+    gdouble* z = ws + L.z;
+    lane_batch<16>(ex, 0, nr, [&](int i) { return z[i] / gq[i]; }, [&](int i, double v) { z[i] = v; });
+    ex.sync();
+  }
+  R.st(IT_TAU, 1.0);
+  R.st(IT_KAP, 1.0);
+  // max(1, ||c~||), c~ = e_J / xe_J;  max(1, ||b / ae||);  max(1, ||h / ge||)
+  R.st(IT_RESX0, BMPC_EQUIL ? fmax(1.0, 1.0 / ws[L.xeq + P.oJ]) : 1.0);
+  {
+    const gdouble* bv = ws + L.bvec;
+    const gdouble* aq = ws + L.aeq;
+    R.st(IT_RESY0, fmax(1.0, sqrt(lane_sum(ex, 0, neq, [&](int i) {
+      const double v = BMPC_EQUIL ? bv[i] / aq[i] : bv[i];
+      return v * v;
+    }))));
+  }
+  {
+    const gdouble* hv = ws + L.hvec;
+    const gdouble* gq = ws + L.geq;
+    R.st(IT_RESZ0, fmax(1.0, sqrt(lane_sum(ex, 0, nr, [&](int i) {
+      const double v = BMPC_EQUIL ? hv[i] / gq[i] : hv[i];
+      return v * v;
+    }))));
+  }
+  R.st(IT_BEST, 1e300);
+  R.st(IT_BEST_TAU, 1.0);
+  R.st(IT_BEST_IT, 0.0);
+  BMPC_TOC(ws, L, PROF_INIT, t_init);
+  R.st(IT_BS_PRES, 0.0), R.st(IT_BS_DRES, 0.0), R.st(IT_BS_RELGAP, 0.0), R.st(IT_BS_GAP, 0.0), R.st(IT_BS_PCOST, 0.0);
+  R.st(IT_BS_OK_CX, 0.0);
+
+  for (int it = 0; it <= P.desc.maxit; ++it) {
+#if defined(BMPC_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
+    {   // probe: latency of one dependent global load under the kernel's own load
+      BMPC_TIC(t_lat);
+      const double probe = *(volatile const gdouble*)(ws + LL().bestx + ex.lane);
+      if (probe == 1.2345e300) ws[LL().prof + PROF_STEP] += 0.0;
+      BMPC_TOC(ws, L, PROF_STEP, t_lat);
+    }
+#endif
+    BMPC_TIC(t_res);
+    // residuals
+    apply_AT<X, NX, NU>(ex, C, ws + LL().y, ws + LL().rx);
+    apply_GT<X, NX, NU>(ex, C, ws + LL().z, ws + LL().ta);
+    // the norms and dot products are accumulated in the passes that produce rx, ry, rz
+    double acx[2] = {0.0, 0.0}, acy[3] = {0.0, 0.0, 0.0}, acz[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    // each pass also forms its residual's and iterate's equilibrated norms (r / xe, xe x, ...)
+    {
+      const gdouble* x = ws + LL().x;
+      const gdouble* xq = ws + LL().xeq;
+      const gdouble* tA = ws + LL().ta;
+      gdouble* rx = ws + LL().rx;
+      gdouble* tA2 = ws + LL().ta2;
+      const double tau = R.ld(IT_TAU);
+      struct R2b { double v, rs, xs; };
+      lane_batch<8>(ex, 0, nv, [&](int i) {
+        const double xi = x[i], q = BMPC_EQUIL ? xq[i] : 1.0;
+        const double v = rx[i] + (tA[i] + (i == P.oJ ? tau : 0.0));
+        return R2b{v, v / q, q * xi};
+      }, [&](int i, R2b r) {
+        rx[i] = r.v;
+        if (BMPC_IPM_LEAN_PASSES) tA2[i] = -r.v;   // the affine direction's right-hand side, formed with rx
+        acx[0] += r.rs * r.rs;
+        acx[1] += r.xs * r.xs;
+      });
+    }
+    apply_A<X, NX, NU>(ex, C, ws + LL().x, ws + LL().ry);
+    {
+      const gdouble* y = ws + LL().y;
+      const gdouble* bv = ws + LL().bvec;
+      const gdouble* aq = ws + LL().aeq;
+      gdouble* ry = ws + LL().ry;
+      const double tau = R.ld(IT_TAU);
+      struct R4 { double v, rs, a, ys; };
+      lane_batch<8>(ex, 0, neq, [&](int i) {
+        const double yi = y[i], bi = bv[i], q = BMPC_EQUIL ? aq[i] : 1.0;
+        const double v = bi * tau - ry[i];
+        return R4{v, v / q, bi * yi, q * yi};
+      }, [&](int i, R4 r) { ry[i] = r.v; acy[0] += r.rs * r.rs; acy[1] += r.a; acy[2] += r.ys * r.ys; });
+    }
+    apply_G<X, NX, NU>(ex, C, ws + LL().x, ws + LL().rz);
+    {
+      const gdouble* z = ws + LL().z;
+      const gdouble* s = ws + LL().s;
+      const gdouble* hv = ws + LL().hvec;
+      const gdouble* gq = ws + LL().geq;
+      gdouble* rz = ws + LL().rz;
+      const double tau = R.ld(IT_TAU);
+      struct R7 { double v, rs, a, zs, ss, sz; };
+      lane_batch<4>(ex, 0, nr, [&](int i) {
+        const double zi = z[i], si = s[i], hi = hv[i], q = BMPC_EQUIL ? gq[i] : 1.0;
+        const double v = hi * tau - rz[i] - si;
+        return R7{v, v / q, hi * zi, q * zi, si / q, si * zi};
+      }, [&](int i, R7 r) { rz[i] = r.v; acz[0] += r.rs * r.rs; acz[1] += r.a; acz[2] += r.zs * r.zs; acz[3] += r.ss * r.ss; acz[4] += r.sz; });
+    }
+    ex.sync();
+    // the ten sums in one reduction (one barrier pair on a multi-wave executor)
+    double rsum[10] = {acy[1], acz[1], acx[1], acy[2], acz[2], acz[3], acz[4], acy[0], acz[0], acx[0]};
+    ex.template sum_n<10>(rsum);
+    // (the scalars of the exit tests live from here to the tests only)
+    const double tau = R.ld(IT_TAU), kap = R.ld(IT_KAP);
+    const double cx = ws[LL().x + P.oJ];
+    const double by = rsum[0], hz = rsum[1];
+    const double rt = kap + cx + by + hz;
+    const double nx = sqrt(rsum[2]), ny = sqrt(rsum[3]);
+    const double nz = sqrt(rsum[4]), ns = sqrt(rsum[5]);
+    const double sz = rsum[6];
+    const double kt = kap * tau;
+    const double mu = (sz + kt) / ((double)(P.nlp + P.ncones) + 1.0);
+    R.st(IT_RT, rt);
+    R.st(IT_MU, mu);
+    R.st(IT_KT, kt);
+    const double gap = sz / (tau * tau);
+    const double pcost = cx / tau, dcost = -(hz + by) / tau;
+    double relgap = -1.0;   // -1 = NaN
+    if (pcost < 0.0) relgap = gap / (-pcost);
+    else if (dcost > 0.0) relgap = gap / dcost;
+    const double nry = neq ? sqrt(rsum[7]) / fmax(R.ld(IT_RESY0) + nx, 1.0) : 0.0;
+    const double nrz = sqrt(rsum[8]) / fmax(R.ld(IT_RESZ0) + nx + ns, 1.0);
+    const double pres = fmax(nry, nrz) / tau;
+    const double dres = sqrt(rsum[9]) / fmax(R.ld(IT_RESX0) + ny + nz, 1.0) / tau;
+    BMPC_TOC(ws, L, PROF_RESID, t_res);
+    const double reltol = P.desc.reltol;
+    // infeasibility certificates (only evaluated when their preconditions hold)
+    double pinfres = -1.0, dinfres = -1.0;
+    if ((hz + by) / fmax(ny + nz, 1.0) < -reltol) {
+      const gdouble* rx = ws + LL().rx;
+      const gdouble* xq = ws + LL().xeq;
+      gdouble* ra = ws + LL().ra;
+      lane_batch<16>(ex, 0, nv, [&](int i) { return (rx[i] - (i == P.oJ ? tau : 0.0)) / (BMPC_EQUIL ? xq[i] : 1.0); },
+                     [&](int i, double v) { ra[i] = v; });
+      ex.sync();
+      pinfres = sqrt(vdot(ex, ra, ra, nv)) / fmax(ny + nz, 1.0);
+    }
+    if (cx / fmax(nx, 1.0) < -reltol) {
+      const gdouble* rb = ws + LL().rb;
+      const gdouble* aq = ws + LL().aeq;
+      const gdouble* gq = ws + LL().geq;
+      const gdouble* s = ws + LL().s;
+      gdouble* ra = ws + LL().ra;
+      apply_A<X, NX, NU>(ex, C, ws + LL().x, ws + LL().rb);
+      const double a1 = sqrt(lane_sum(ex, 0, neq, [&](int i) {
+        const double v = rb[i] / (BMPC_EQUIL ? aq[i] : 1.0);
+        return v * v;
+      })) / fmax(nx, 1.0);
+      apply_G<X, NX, NU>(ex, C, ws + LL().x, ra);
+      lane_batch<16>(ex, 0, nr, [&](int i) { return (ra[i] + s[i]) / (BMPC_EQUIL ? gq[i] : 1.0); },
+                     [&](int i, double v) { ra[i] = v; });
+      ex.sync();
+      const double a2 = sqrt(vdot(ex, ra, ra, nr)) / fmax(nx + ns, 1.0);
+      dinfres = fmax(a1, a2);
+    }
+    auto check = [&](double ft, double at, double rtl) -> int {
+      if (!(tau > 0.0 && kap >= 0.0)) return 99;
+      if ((-cx > 0.0 || -by - hz >= -at) && pres < ft && dres < ft &&
+          (gap < at || (relgap >= 0.0 && relgap < rtl)))
+        return EXIT_OPTIMAL;
+      if (dinfres >= 0.0 && dinfres < ft && tau < kap) return EXIT_DINF;
+      if ((pinfres >= 0.0 && pinfres < ft && tau < kap) ||
+          (tau < ft && kap < ft && pinfres >= 0.0 && pinfres < ft))
+        return EXIT_PINF;
+      return 99;
+    };
+    const double score = fmax(fmax(pres, dres), relgap >= 0.0 ? relgap : 1e300);
+    if (score < R.ld(IT_BEST)) {
+      R.st(IT_BEST, score);
+      R.st(IT_BEST_IT, (double)it);
+      R.st(IT_BEST_TAU, tau);
+      R.st(IT_BS_PRES, pres), R.st(IT_BS_DRES, dres), R.st(IT_BS_RELGAP, relgap), R.st(IT_BS_GAP, gap), R.st(IT_BS_PCOST, pcost);
+      R.st(IT_BS_OK_CX, (-cx > 0.0 || -by - hz >= -5e-5) ? 1.0 : 0.0);
+      if (ex.lane == 0) {   // mirror for the guard below
+        ws[LL().misc + MISC_BEST] = score;
+        ws[LL().misc + MISC_BEST + 1] = tau;
+      }
+      const gdouble* x = ws + LL().x;
+      lane_batch<16>(ex, 0, nv, [&](int i) { return x[i]; }, [&](int i, double v) { ws[LL().bestx + i] = v; });
+      ex.sync();
+    }
+    BMPC_TRACE("it %3d pcost %+.16e dcost %+.16e gap %.16e pres %.16e dres %.16e kap %.16e tau %.16e"
+               " nx %.16e ny %.16e nz %.16e ns %.16e best %.3e\n",
+               it, pcost, dcost, gap, pres, dres, kap, tau, nx, ny, nz, ns, R.ld(IT_BEST));
+    int code = check(P.desc.feastol, P.desc.abstol, reltol);
+    if (code == 99 && it == P.desc.maxit) {
+      const int c2 = check(1e-4, 5e-5, 5e-5);
+      code = c2 == 99 ? EXIT_MAXIT : c2 + EXIT_INACC;
+    }
+    if (code != 99) BMPC_TRACE("   code %d (it %d)\n", code, it);
+    if (code != 99) {
+      const gdouble* x = ws + LL().x;
+      lane_batch<16>(ex, 0, nv, [&](int i) { return x[i] / tau; }, [&](int i, double v) { ws[LL().sol + i] = v; });
+      ex.sync();
+      res.exit_flag = code;
+      res.iters = it;
+      res.pcost = pcost;
+      return res;
+    }
+    // refinement only once the iterate nears the tolerances: an unrefined direction is
+    // accurate to ~1e-12 relative, far below what the early steps need (a scalar: held in an
+    // SGPR across the calls below)
+    const int nref = ex.uniform(score < BMPC_REFSCORE2) ? BMPC_NITREF2 : ex.uniform(score < BMPC_REFSCORE) ? BMPC_NITREF : 0;
+    // ---- Newton step ---------------------------------------------------------------------
+    // the phase results are wave-uniform (each ends in a wave reduction); ex.uniform makes the
+    // branches scalar, so no phase is ever called under a partial exec mask
+    bool ok = ex.uniform(compute_scaling(ex, C, ws + LL().s, ws + LL().z));
+    if (ok) ok = ex.uniform(kkt_factor<X, NX, NU>(ex, C, false));
+    if (ok) {
+      // right-hand sides of the c direction (-c, bvec, hvec) and the affine direction
+      // (-rx, ry, rb = rz - W xi = rz + W lam for xi = -lam), solved together with the
+      // Woodbury columns (kkt_solve_pair)
+      gdouble* ej = BMPC_IPM_LEAN_PASSES ? ws + LL().ej : ws + LL().ta;
+#if !BMPC_IPM_LEAN_PASSES   // else ej holds -e_J since the initial point, and the residual pass formed tA2 = -rx
+      {
+        const gdouble* rx = ws + LL().rx;
+        gdouble* tA2 = ws + LL().ta2;
+        lane_batch<16>(ex, 0, nv, [&](int i) { return i == P.oJ ? -1.0 : 0.0; }, [&](int i, double v) { ej[i] = v; });
+        lane_batch<16>(ex, 0, nv, [&](int i) { return -rx[i]; }, [&](int i, double v) { tA2[i] = v; });
+      }
+#endif
+      apply_W(ex, C, 0, ws + LL().lam, ws + LL().rb, 1.0, ws + LL().rz, 1.0);
+#if BMPC_FLAT_PAIR
+      kkt_pair_rhs<X, NX, NU>(ex, C, ej, ws + LL().ta2, ws + LL().rb);
+      ok = ex.uniform(kkt_coupling<X, NX, NU>(ex, C, 2));
+      if (ok) {
+        kkt_pair_back<X, NX, NU>(ex, C, nref == 0);
+        if (nref > 0) {
+#if BMPC_PAIR_REFINE
+          kkt_refine_pair<X, NX, NU>(ex, C, ej, ws + LL().bvec, ws + LL().k_t3, ws + LL().x1, ws + LL().y1, ws + LL().z1, ws + LL().ta2,
+                                     ws + LL().ry, ws + LL().k_t3b, ws + LL().x2, ws + LL().y2, ws + LL().z2, nref);
+#else
+          kkt_refine<X, NX, NU>(ex, C, ej, ws + LL().bvec, ws + LL().k_t3, ws + LL().x1, ws + LL().y1, ws + LL().z1, nref);
+          kkt_refine<X, NX, NU>(ex, C, ws + LL().ta2, ws + LL().ry, ws + LL().k_t3b, ws + LL().x2, ws + LL().y2, ws + LL().z2, nref);
+#endif
+        }
+      }
+#else
+      ok = ex.uniform(kkt_solve_pair<X, NX, NU>(ex, C, ej, ws + LL().ta2, ws + LL().rb, nref));
+#endif
+    }
+    if (ok) {
+#if BMPC_IPM_LEAN_PASSES
+      double by1, by2;   // bv'y1 + hv'z1 and bv'y2 + hv'z2 in one pass over bv and hv
+      dot2_pair(ex, ws + LL().bvec, ws + LL().y1, ws + LL().y2, neq, ws + LL().hvec, ws + LL().z1, ws + LL().z2, nr, by1, by2);
+#else
+      const double by1 = dot2(ex, ws + LL().bvec, ws + LL().y1, neq, ws + LL().hvec, ws + LL().z1, nr),
+                   by2 = dot2(ex, ws + LL().bvec, ws + LL().y2, neq, ws + LL().hvec, ws + LL().z2, nr);
+#endif
+      {
+        const double tau = R.ld(IT_TAU), kap = R.ld(IT_KAP);
+        const double den = kap / tau - (ws[LL().x1 + P.oJ] + by1);
+        const double dk_aff = -R.ld(IT_KT);
+        const double dtau_a = (R.ld(IT_RT) + dk_aff / tau + ws[LL().x2 + P.oJ] + by2) / den;
+        R.st(IT_DEN, den);
+        R.st(IT_DTAU_A, dtau_a);
+        R.st(IT_DKAP_A, (dk_aff - kap * dtau_a) / tau);
+      }
+      // dz_aff = z2 + dtau_a z1, rb = W dz_aff, ds = dsW_aff = xi - W dz_aff (one pass)
+      const LpSteps lpa = affine_dirs(ex, C, ws + LL().z2, ws + LL().z1, R.ld(IT_DTAU_A), ws + LL().lam, ws + LL().rb, ws + LL().ds);
+      double a_aff = max_step2<X, BMPC_IPM_LEAN_PASSES != 0>(ex, C, ws + LL().lam, ws + LL().ds, ws + LL().rb, lpa.a1, lpa.a2);
+      {
+        const double tau = R.ld(IT_TAU), kap = R.ld(IT_KAP);
+        const double dtau_a = R.ld(IT_DTAU_A), dkap_a = R.ld(IT_DKAP_A);
+        if (dtau_a < 0.0) a_aff = fmin(a_aff, -tau / dtau_a);
+        if (dkap_a < 0.0) a_aff = fmin(a_aff, -kap / dkap_a);
+        a_aff = fmax(0.0, fmin(a_aff, 0.999));
+        double sigma = (1.0 - a_aff) * (1.0 - a_aff) * (1.0 - a_aff);
+        sigma = fmin(1.0, fmax(1e-4, sigma));
+        const double eta1 = 1.0 - sigma;
+        const double smu = sigma * R.ld(IT_MU);
+        R.st(IT_SIGMA, sigma);
+        R.st(IT_ETA1, eta1);
+        R.st(IT_SMU, smu);
+        // combined: ds_comb = -lam o lam - dsW_a o Wdz_a + sigma mu e, xi = lam \ ds_comb (kept in
+        // ds), rb = eta1 rz - W xi (one pass)
+        combined_rhs(ex, C, ws + LL().lam, ws + LL().ds, ws + LL().rb, ws + LL().rz, smu, eta1);
+      }
+      {
+        const gdouble* rx = ws + LL().rx;
+        const gdouble* ry = ws + LL().ry;
+        gdouble* tA = ws + LL().ta;
+        gdouble* ya = ws + LL().ya;
+        const double eta1 = R.ld(IT_ETA1);
+        lane_batch<16>(ex, 0, nv, [&](int i) { return -eta1 * rx[i]; }, [&](int i, double v) { tA[i] = v; });
+        lane_batch(ex, 0, neq, [&](int i) { return eta1 * ry[i]; }, [&](int i, double v) { ya[i] = v; });
+        ex.sync();
+      }
+      kkt_solve_flat<X, NX, NU>(ex, C, ws + LL().ta, ws + LL().ya, ws + LL().rb, ws + LL().x2, ws + LL().y2, ws + LL().z2, nref);
+      {
+        const double d2 = dot2(ex, ws + LL().bvec, ws + LL().y2, neq, ws + LL().hvec, ws + LL().z2, nr);
+        const double tau = R.ld(IT_TAU);
+        const double dk_c = -R.ld(IT_KT) - R.ld(IT_DTAU_A) * R.ld(IT_DKAP_A) + R.ld(IT_SMU);
+        const double dtau = (R.ld(IT_ETA1) * R.ld(IT_RT) + dk_c / tau + ws[LL().x2 + P.oJ] + d2) / R.ld(IT_DEN);
+        R.st(IT_DTAU, dtau);
+        R.st(IT_DKAP, (dk_c - R.ld(IT_KAP) * dtau) / tau);
+      }
+      double nonfinite = 0.0;   // the step's finiteness check, taken in the pass that forms dx
+#if !BMPC_IPM_LEAN_PASSES
+      {
+        const gdouble* x1 = ws + LL().x1;
+        const gdouble* y1 = ws + LL().y1;
+        gdouble* x2 = ws + LL().x2;
+        gdouble* y2 = ws + LL().y2;
+        const double dtau = R.ld(IT_DTAU);
+        lane_batch<8>(ex, 0, nv, [&](int i) { return x2[i] + (dtau * x1[i]); }, [&](int i, double v) {
+          x2[i] = v;
+          if (!isfinite(v)) nonfinite = 1.0;
+        });
+        lane_batch(ex, 0, neq, [&](int i) { return y2[i] + (dtau * y1[i]); }, [&](int i, double v) { y2[i] = v; });
+        ex.sync();
+      }
+#endif
+      // dz = z2 + dtau z1, rb = W dz, ds = dsW = xi - W dz, rc = W dsW = ds (one pass)
+      const LpSteps lpc = combined_dirs(ex, C, ws + LL().z2, ws + LL().z1, R.ld(IT_DTAU), ws + LL().ds, ws + LL().rb, ws + LL().rc);
+      double a = max_step2<X, BMPC_IPM_LEAN_PASSES != 0>(ex, C, ws + LL().lam, ws + LL().ds, ws + LL().rb, lpc.a1, lpc.a2);
+      const double dtau = R.ld(IT_DTAU), dkap = R.ld(IT_DKAP);
+      {
+        const double tau = R.ld(IT_TAU), kap = R.ld(IT_KAP);
+        if (dtau < 0.0) a = fmin(a, -tau / dtau);
+        if (dkap < 0.0) a = fmin(a, -kap / dkap);
+      }
+      a = fmin(a, 0.999);
+      const double alpha = ex_uniform(ex, a * 0.99);   // never step onto or past the cone / tau / kappa boundary
+#if BMPC_IPM_LEAN_PASSES
+      // dx = x2 + dtau x1 and dy = y2 + dtau y1 are formed in the update's own passes (nothing
+      // else reads them; alpha does not depend on them).  A non-finite dx is seen after x was
+      // written: the backtrack below then leaves through the best iterate and x is dead.
+      ok = ex.uniform(isfinite(dtau) && alpha > 1e-10);
+      if (ok) {
+        const gdouble* x1 = ws + LL().x1;
+        const gdouble* x2 = ws + LL().x2;
+        gdouble* x = ws + LL().x;
+        lane_batch<8>(ex, 0, nv, [&](int i) {
+          const double v = x2[i] + (dtau * x1[i]);
+          if (!isfinite(v)) nonfinite = 1.0;   // (a batch's clamped slots repeat an element of the lane)
+          return x[i] + (alpha * v);
+        }, [&](int i, double v) { x[i] = v; });
+        ok = ex.uniform(ex.max(nonfinite) == 0.0);
+      }
+#else
+      const double fin = ex.max(nonfinite);
+      ok = ex.uniform(fin == 0.0 && isfinite(dtau) && alpha > 1e-10);
+#endif
+      BMPC_TRACE("   step den %.16e dtau_a %.16e a_aff %.16e sigma %.16e dtau %.16e alpha %.16e nref %d ok %d\n",
+                 R.ld(IT_DEN), R.ld(IT_DTAU_A), a_aff, R.ld(IT_SIGMA), dtau, alpha, nref, (int)ok);
+      if (ok) {
+        {
+          const gdouble* y1 = ws + LL().y1;
+          const gdouble* y2 = ws + LL().y2;
+          gdouble* y = ws + LL().y;
+#if BMPC_IPM_LEAN_PASSES
+          lane_batch(ex, 0, neq, [&](int i) { return y[i] + (alpha * (y2[i] + (dtau * y1[i]))); },
+                     [&](int i, double v) { y[i] = v; });
+#else
+          const gdouble* x2 = ws + LL().x2;
+          gdouble* x = ws + LL().x;
+          (void)y1;
+          lane_batch<8>(ex, 0, nv, [&](int i) { return x[i] + (alpha * x2[i]); }, [&](int i, double v) { x[i] = v; });
+          lane_batch(ex, 0, neq, [&](int i) { return y[i] + (alpha * y2[i]); }, [&](int i, double v) { y[i] = v; });
+#endif
+        }
+        {
+          const gdouble* z2 = ws + LL().z2;
+          const gdouble* rc = ws + LL().rc;
+          gdouble* z = ws + LL().z;
+          gdouble* s = ws + LL().s;
+          struct ZS { double z, s; };
+          lane_batch<4>(ex, 0, nr, [&](int i) { return ZS{z[i] + alpha * z2[i], s[i] + alpha * rc[i]}; },
+                     [&](int i, ZS v) { z[i] = v.z; s[i] = v.s; });
+        }
+        R.st(IT_TAU, R.ld(IT_TAU) + alpha * dtau);
+        R.st(IT_KAP, R.ld(IT_KAP) + alpha * dkap);
+        ex.sync();
+      }
+    }
+    if (!ok) {   // numerical failure: ECOS backtracks to the best iterate
+      const double best_score = R.ld(IT_BEST), best_tau = R.ld(IT_BEST_TAU);
+      BMPC_TRACE("   backtrack (it %d) to the best iterate (it %d, score %.3e)\n", it, (int)R.ld(IT_BEST_IT), best_score);
+      // guard: the best iterate's score and tau are held in the iteration record across every
+      // phase call of the loop; a build that lost them there (an LDS area overlapping another's,
+      // DESIGN.md §5) is reported as EXIT_GUARD instead of returning a wrong point
+      if (best_score < 1e300 && (ws[LL().misc + MISC_BEST] != best_score || ws[LL().misc + MISC_BEST + 1] != best_tau)) {
+        res.exit_flag = EXIT_GUARD;
+        res.iters = it;
+        return res;
+      }
+      const double bs_relgap = R.ld(IT_BS_RELGAP);
+      const bool inacc = R.ld(IT_BS_OK_CX) != 0.0 && R.ld(IT_BS_PRES) < 1e-4 && R.ld(IT_BS_DRES) < 1e-4 &&
+                         (R.ld(IT_BS_GAP) < 5e-5 || (bs_relgap >= 0.0 && bs_relgap < 5e-5));
+      lane_batch<16>(ex, 0, nv, [&](int i) { return ws[LL().bestx + i] / best_tau; }, [&](int i, double v) { ws[LL().sol + i] = v; });
+      ex.sync();
+      res.exit_flag = inacc ? EXIT_OPTIMAL + EXIT_INACC : EXIT_NUMERICS;
+      res.iters = it;
+      res.pcost = R.ld(IT_BS_PCOST);
+      return res;
+    }
+  }
+  return res;
+}
+#endif   // BMPC_ITER_RECORD
+// The loop with its state in locals: the BMPC_ITER_RECORD=0 text, and in every build the loop of the
+// executors with kIterRecord = false -- the multi-wave small-batch kernel, whose every-exit loop
+// (tests/test_iter_record_gpu.py, N=4 NB=1) did not keep the parent's results on the record's text.
+template <class X, int NX, int NU>
+BMPC_HD IpmResult ipm_solve_locals(const X ex, const Ctx& C) {
   CPlan& P = *C.P;
   CLayout& L = *C.L;
   gdouble* ws = C.ws;
@@ -4226,6 +4755,19 @@ BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
     }
   }
   return res;
+}
+
+template <class X, class = void>
+struct iter_record { static constexpr bool value = BMPC_ITER_RECORD != 0; };
+template <class X>
+struct iter_record<X, decltype((void)X::kIterRecord)> { static constexpr bool value = BMPC_ITER_RECORD != 0 && X::kIterRecord; };
+template <class X, int NX, int NU>
+BMPC_HD IpmResult ipm_solve(const X ex, const Ctx& C) {
+#if BMPC_ITER_RECORD
+  if constexpr (iter_record<X>::value) return ipm_solve_record<X, NX, NU>(ex, C);
+  else
+#endif
+    return ipm_solve_locals<X, NX, NU>(ex, C);
 }
 
 }  // namespace bmpc

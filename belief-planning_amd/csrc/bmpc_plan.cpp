@@ -325,10 +325,16 @@ std::string build_plan(const bmpc_plan_desc& desc, HostPlan& hp) {
   P.nconst = P.lds_fu + P.nFu * d;
   P.lds_scr = std::max(64, (P.nconst + 7) & ~7);
   // (plans whose staging does not fit form each node's slack terms inside the tree solve's sweep)
-  P.nscr = desc.controller == BMPC_CTRL_CVAR && P.lds_scr + ncoup + T * P.Nc <= 1248 ? T * P.Nc : 0;
+  // the IPM's iteration record (BMPC_ITER_LDS doubles): in the unused tail of the first area where
+  // that is large enough, else appended after the staging area -- before the pivots either way, so
+  // a lean launch has it
+  const bool it_tail = P.lds_scr - P.nconst >= BMPC_ITER_LDS;
+  const int nit = desc.controller == BMPC_CTRL_CVAR && !it_tail ? BMPC_ITER_LDS : 0;
+  P.nscr = desc.controller == BMPC_CTRL_CVAR && P.lds_scr + nit + ncoup + T * P.Nc <= 1248 ? T * P.Nc : 0;
+  P.lds_it = it_tail ? P.nconst : P.lds_scr + P.nscr;
   // pivots and right-hand sides before the matrix: lean launches keep those in LDS too (the
   // substitutions' dependent chains then run on LDS; only the matrix moves to the slab)
-  P.lds_piv = P.lds_scr + P.nscr;
+  P.lds_piv = P.lds_scr + P.nscr + nit;
   P.lds_rhs = P.lds_piv + P.nsm;
   P.lds_rhs2 = P.lds_rhs + P.nsm;   // the pair's second right-hand side (kkt_back_pair)
   P.lds_M = P.lds_rhs2 + P.nsm;
