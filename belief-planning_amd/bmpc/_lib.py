@@ -37,7 +37,7 @@ def sources():
     solver kernels (compiled in parallel), the host-side plan builders."""
     srcs = [os.path.join(CSRC, f) for f in ("bmpc_hip.hip", "bmpc_k_highway.hip", "bmpc_k_highway_t.hip",
                                             "bmpc_k_merge.hip", "bmpc_k_merge_loop.hip", "bmpc_k_quadruped.hip",
-                                            "bmpc_k_quad_loop.hip", "bmpc_kb_highway.hip",
+                                            "bmpc_k_quad_loop.hip", "bmpc_k_highway_qp_loop.hip", "bmpc_kb_highway.hip",
                                             "bmpc_kb_highway_t.hip", "bmpc_kb_merge.hip", "bmpc_kb_quadruped.hip",
                                             "bmpc_plan.cpp", "bmpc_qpplan.cpp")]
     if _phased():

@@ -111,3 +111,25 @@ def exact_expectation(values, logp):
     f, lw = _args(values, logp)
     w = np.exp(lw)
     return float((w * f).sum()), float(w.sum())
+
+
+def paired_difference(a, b):
+    """(mean of a - b, its standard error, the sample correlation of a and b) for per-ego values of
+    two runs over the same episodes (scenarios.controller_comparison: the same initial states and
+    the same seeds, so ego e of both runs meets the same draws).  The standard error is that of the
+    sample mean of the differences, sqrt(var(a - b) / n) with the n - 1 variance (0 for n = 1): the
+    positive correlation of paired episodes is what makes it smaller than that of two independent
+    runs.  The correlation is nan when either side is constant.  Plain and unweighted on purpose:
+    the log-weights of a tilted run are likelihood ratios of each ego's realised choice sequence,
+    which depend on the states the choices were drawn at, hence on the controller -- two controllers'
+    weighted runs have different weights per ego, and a difference of their per-ego values is no
+    estimate of anything; compare montecarlo.estimate's two results instead."""
+    x, y = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
+    if x.shape != y.shape or x.size == 0:
+        raise ValueError(f"a and b must hold one entry per ego, got {x.shape} and {y.shape}")
+    d = x - y
+    n = d.size
+    se = float(np.sqrt(d.var(ddof=1) / n)) if n > 1 else 0.0
+    sx, sy = x.std(), y.std()
+    corr = float(((x - x.mean()) * (y - y.mean())).mean() / (sx * sy)) if sx > 0 and sy > 0 else float("nan")
+    return float(d.mean()), se, corr

@@ -220,7 +220,8 @@ class BatchPlan:
                     J_ptr, status_ptr, iters_ptr, stats_ptr=None, stream=None):
         """nsteps closed-loop steps of every ego (bmpc_loop_device): env_step_device(t) then
         solve_device for t = t0 .. t0+nsteps-1, the same results; one fused launch (k_loop) when
-        the batch takes the one-wave IPM.  Async on `stream`."""
+        a CVaR batch takes the one-wave IPM and for BranchMPC (CTRL_QP) plans at any batch; robust
+        plans keep their launches per step unless BMPC_LOOP_FUSED=2.  Async on `stream`."""
         vp = _vp(scene_ptr, upred_ptr, x_ptr, z_ptr, xref_ptr, J_ptr, status_ptr, iters_ptr, stats_ptr, stream)
         check(lib().bmpc_loop_device(self._h, C.byref(env), int(t0), int(nsteps), *vp), "bmpc_loop_device")
 

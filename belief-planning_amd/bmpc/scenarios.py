@@ -7,20 +7,29 @@ import numpy as np
 from . import abi
 
 
-def highway_desc(N=20, NB=1, N_lane=4, am=6.0, rm=0.3, L=4.0, W=2.5, s1=2.0, model_lanes=3):
-    """initBranchMPC(n=4,d=2,N,NB,...) + Branch_constants of main_branch.py:37."""
+# the overtake scene's three controllers (main_branch.py): BranchMPC_CVaR, BranchMPC (the expected-cost
+# branch MPC, MPC_branch.py:881) and robustMPC
+HIGHWAY_CONTROLLERS = {"cvar": abi.CTRL_CVAR, "branch": abi.CTRL_QP, "robust": abi.CTRL_ROBUST}
+
+
+def highway_desc(N=20, NB=1, N_lane=4, am=6.0, rm=0.3, L=4.0, W=2.5, s1=2.0, model_lanes=3, controller="cvar"):
+    """initBranchMPC(n=4,d=2,N,NB,...) + Branch_constants of main_branch.py:37.  controller: "cvar"
+    (BranchMPC_CVaR), "branch" (BranchMPC) or "robust" (robustMPC) -- HIGHWAY_CONTROLLERS."""
+    if controller not in HIGHWAY_CONTROLLERS:
+        raise ValueError(f"controller={controller!r}: one of {sorted(HIGHWAY_CONTROLLERS)}")
     Fx = np.array([[0., 1, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1], [0, 0, 0, -1]])
     bx = np.array([N_lane * 3.6 - W / 2, -W / 2, 0.25, 0.25])
     Fu = np.kron(np.eye(2), np.array([1, -1])).T
     bu = np.array([am, am, rm, rm])
-    return abi.make_desc(abi.CTRL_CVAR, abi.MODEL_HIGHWAY, 4, 2, N, NB, 3, 0.1,
+    return abi.make_desc(HIGHWAY_CONTROLLERS[controller], abi.MODEL_HIGHWAY, 4, 2, N, NB, 3, 0.1,
                          np.diag([0., 3, 3, 10]), np.diag([1., 100]), Fx, bx, Fu, bu, [0., 300.],
                          [L, W, s1, float(model_lanes)], ralpha=0.9)
 
 
-def highway_desc_from_golden(g):
+def highway_desc_from_golden(g, controller="cvar"):
     return highway_desc(N=int(g["N"]), NB=int(g["NB"]), N_lane=int(g["N_lane"]), am=float(g["am"]),
-                        rm=float(g["rm"]), L=float(g["L"]), W=float(g["W"]), s1=float(g["s1"]))
+                        rm=float(g["rm"]), L=float(g["L"]), W=float(g["W"]), s1=float(g["s1"]),
+                        controller=controller)
 
 
 def highway_policy_rows(targets, Kpsi=0.1):
@@ -113,7 +122,8 @@ def overtake_population(B, steps, seed=0, device=0, record=False):
     booked by the next step, so they cover steps - 1 solves) and the final scene [B, ENV_STRIDE];
     with `record` also the per-step record on the host (plan.LoopRecording: row t holds step t,
     the last row's scene is the returned one).  The obstacle follows the reference's deterministic
-    rule; sampled_overtake_population draws its policy from the model's branch distribution."""
+    rule; sampled_overtake_population draws its policy from the model's branch distribution (and
+    takes a plan description: desc=highway_desc(controller="branch") runs BranchMPC)."""
     return sampled_overtake_population(B, steps, seed, device, record, obstacle=None)
 
 
@@ -126,7 +136,8 @@ def sampled_overtake_population(B, steps, seed=0, device=0, record=False, obstac
     ego_base + B) and draw as those global egos: a sharded run passes
     ego_base = distributed.shard(population, rank, world)[0] and B = hi - lo on every rank, and each
     ego then has the trajectory it has in the unsharded run.  desc: another highway plan description
-    than highway_desc().  Any draw can be audited on the host with bmpc.rng.obstacle_uniform(
+    than highway_desc() -- highway_desc(controller="branch" | "robust") runs the scene's other two
+    controllers, BranchMPC and robustMPC.  Any draw can be audited on the host with bmpc.rng.obstacle_uniform(
     obstacle_seed, global ego, t // hold)."""
     pl, scene0 = _seeded_plan("overtake", B, seed, device, ego_base, population, desc)
     _attach_obstacle(pl, obstacle, obstacle_seed, hold, ego_base)
@@ -574,3 +585,40 @@ def observed_quadruped_population(B, steps, sigma_x=None, sigma_z=None, observat
     _attach_disturbance(pl, sigma_ego, sigma_obs, disturbance_seed, ego_base)
     _attach_observation(pl, sigma_x, sigma_z, observation_seed, ego_base)
     return _closed_loop(pl, scene0, steps, record, device)
+
+
+def controller_comparison(B, steps, controllers=("cvar", "branch", "robust"), seed=0, device=0, record=False,
+                          obstacle=None, obstacle_seed=0, hold=1, sigma_x=None, sigma_z=None, observation_seed=0,
+                          sigma_ego=None, sigma_obs=None, disturbance_seed=0):
+    """The overtake scene's controllers on one population of episodes: observed_overtake_population
+    once per entry of `controllers` (highway_desc's keywords, each run with
+    desc=highway_desc(controller=c)) with the same seeded initial states and
+    the same obstacle, disturbance and observation seeds -- common random numbers: every draw is
+    addressed by (seed, ego, step), so ego e of one run and ego e of another meet the same noise and,
+    while their states agree, the same obstacle choices, and the episodes are paired across controllers.
+    Returns a dict with
+      "runs":  per controller dict(stats [B, ENV_NSTAT], scene [B, ENV_STRIDE][, record]);
+      "pairs": per pair (a, b) in the order of `controllers`, dict(collided=, cost=) of
+               montecarlo.paired_difference (mean of a - b, its standard error, the correlation) of the
+               egos' collided flags (ENVS_COLLIDED) and mean solve costs (ENVS_J / ENVS_SOLVES).
+    The runs are unweighted (obstacle None or "model"): a tilted run's log-weights depend on the
+    states, hence on the controller, and do not pair (montecarlo.paired_difference)."""
+    from . import montecarlo
+    controllers = tuple(controllers)
+    for c in controllers:
+        if c not in HIGHWAY_CONTROLLERS:
+            raise ValueError(f"controller={c!r}: one of {sorted(HIGHWAY_CONTROLLERS)}")
+    if len(set(controllers)) != len(controllers) or not controllers:
+        raise ValueError("controllers: at least one, each once")
+    runs = {}
+    for c in controllers:
+        out = observed_overtake_population(B, steps, sigma_x, sigma_z, observation_seed, sigma_ego, sigma_obs,
+                                           disturbance_seed, seed, device, record, obstacle, obstacle_seed, hold,
+                                           desc=highway_desc(controller=c))
+        runs[c] = dict(zip(("stats", "scene", "record"), out))
+    collided = {c: r["stats"][:, abi.ENVS_COLLIDED] for c, r in runs.items()}
+    cost = {c: r["stats"][:, abi.ENVS_J] / np.maximum(r["stats"][:, abi.ENVS_SOLVES], 1.0) for c, r in runs.items()}
+    pairs = {(a, b): dict(collided=montecarlo.paired_difference(collided[a], collided[b]),
+                          cost=montecarlo.paired_difference(cost[a], cost[b]))
+             for i, a in enumerate(controllers) for b in controllers[i + 1:]}
+    return dict(runs=runs, pairs=pairs)

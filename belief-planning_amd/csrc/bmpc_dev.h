@@ -453,6 +453,19 @@ __device__ __attribute__((noinline)) void loop_merge_env_step(const bmpc_merge_e
   merge_env_step_slab(env, R, P, L, t, st, ws, up, x, z, xr, opt, e);
 }
 
+// The overtake scene's step for the OSQP-class controllers (BranchMPC, robustMPC; OvertakeQpScene):
+// loop_env_step with the statistics reading their status (1 = solved), the rule k_env applies to a
+// plan that is not CVaR.
+__device__ __attribute__((noinline)) void loop_env_step_qp(const bmpc_env_desc& env, double dt, int N, int m, int t,
+                                                           double* st, bmpc_policy* pol, const double* up, double* x,
+                                                           double* z, double* xr, double Jv, int status, int iters,
+                                                           double* stats, const bmpc_obstacle_sampling& smp,
+                                                           const double* mc, int e, const SceneOptions* opt) {
+  if (t > 0 && stats) env_accumulate(st, Jv, status, iters, false, stats);
+  env_step_ego(env, dt, N, m, t, st, pol, up, x, z, xr, &smp, mc, e, scene_prop(opt), scene_dist(opt),
+               scene_obs(opt));
+}
+
 // The quadruped loop's solve and scene step as calls (OSQP-class controllers: env_accumulate reads
 // their status, 1 = solved).
 template <class X, class M>
@@ -509,6 +522,9 @@ __device__ __attribute__((noinline)) void loop_record_wide(double* upred, double
 #ifndef BMPC_QUAD_LOOP_INLINE_QP
 #define BMPC_QUAD_LOOP_INLINE_QP 1
 #endif
+#ifndef BMPC_OVERTAKE_QP_LOOP_INLINE_QP
+#define BMPC_OVERTAKE_QP_LOOP_INLINE_QP 1
+#endif
 // The scene of a k_loop (its kernel argument): one ego's scene step on lane 0, through an
 // out-of-line call.  The overtake scene re-targets the ego's policies, the merge scene writes the
 // ego's transform slots, the quadruped scene neither.  The overtake and the quadruped scene carry the
@@ -530,6 +546,20 @@ struct OvertakeScene {
                        double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
     loop_env_step(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, P.desc.mc,
                   (int)blockIdx.x, opt);
+  }
+};
+// The overtake scene under BranchMPC or robustMPC (bmpc_k_highway_qp_loop.hip): OvertakeScene's step
+// with the QP solver and the OSQP-class statistics (both forms of the solve measured).
+struct OvertakeQpScene {
+  static constexpr bool kQp = true;
+  static constexpr bool kInlineIpm = BMPC_OVERTAKE_QP_LOOP_INLINE_QP != 0;
+  bmpc_env_desc env;
+  bmpc_obstacle_sampling smp;
+  const SceneOptions* opt;
+  __device__ void step(const Plan& P, const Layout&, int t, double* st, bmpc_policy* pe, double*, const double* up,
+                       double* x, double* z, double* xr, double Jv, int status, int iters, double* stats) const {
+    loop_env_step_qp(env, P.desc.dt, P.N, P.m, t, st, pe, up, x, z, xr, Jv, status, iters, stats, smp, P.desc.mc,
+                     (int)blockIdx.x, opt);
   }
 };
 struct MergeScene {
@@ -759,13 +789,16 @@ LaunchFn launch_tree_highway, launch_solver_highway, launch_solver_blk_highway;
 LaunchFn launch_tree_highway_t, launch_solver_highway_t, launch_solver_blk_highway_t;
 LaunchFn launch_tree_merge, launch_solver_merge, launch_solver_blk_merge;
 LaunchFn launch_tree_quadruped, launch_solver_quadruped, launch_solver_blk_quadruped;
-// the fused closed loops (bmpc_k_highway.hip, bmpc_k_merge_loop.hip, bmpc_k_quad_loop.hip)
+// the fused closed loops (bmpc_k_highway.hip, bmpc_k_merge_loop.hip, bmpc_k_quad_loop.hip,
+// bmpc_k_highway_qp_loop.hip: the overtake scene under an OSQP-class controller)
 hipError_t launch_loop_highway(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
                                double* stats);
 hipError_t launch_loop_merge(const SolveLaunch& a, const bmpc_merge_env_desc& env, const MergeRef& ref, int t0,
                              int nsteps, double* scene, double* stats);
 hipError_t launch_loop_quad(const SolveLaunch& a, const bmpc_quad_env_desc& env, int t0, int nsteps, double* scene,
                             double* stats);
+hipError_t launch_loop_highway_qp(const SolveLaunch& a, const bmpc_env_desc& env, int t0, int nsteps, double* scene,
+                                  double* stats);
 
 #if defined(BMPC_WITH_PHASED)
 // The phase-per-kernel CVaR IPM (experimental/bmpc_dev_ph.h, bmpc_kp_*.hip; tools-only builds with

@@ -921,9 +921,11 @@ struct LaunchChoice {
 // takes this path (default: one ego per CU; 0 disables it); BMPC_BLOCK_WAVES: 4 or 8;
 // BMPC_BLK_LDS=0: the small-batch kernel keeps every array in the slab.
 // Larger CVaR batches may fuse a closed loop into one launch, unless a policy tracks the lane
-// reference or BMPC_LOOP_FUSED=0 asks for the per-step launches (A/B).  qp_loop: the caller is the
-// quadruped loop, whose k_loop runs the QP solver -- its OSQP-class plans fuse too (no other loop
-// has a k_loop for them: robust overtake plans keep their launches per step).
+// reference or BMPC_LOOP_FUSED=0 asks for the per-step launches (A/B).  qp_loop: the caller's loop
+// has a k_loop that runs the QP solver (the quadruped loop, the overtake loop) -- its OSQP-class
+// plans fuse too, at any batch (they have no small-batch kernel), except the overtake loop's robust
+// plans, which keep their launches per step unless BMPC_LOOP_FUSED=2 asks for every plan that has
+// a k_loop to fuse.
 static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform, bool qp_loop = false) {
   const Plan& P = pl->hp.plan;
   const bmpc_ctx* c = pl->ctx;
@@ -949,7 +951,9 @@ static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform, bool qp_loop 
     if (want > ch.lds_bytes && want <= c->lds_per_cu) ch.lds_bytes = want;
   }
   const char* ef = getenv("BMPC_LOOP_FUSED");
-  ch.fused_loop = (cvar || qp_loop) && !pl->psiref && !(ef && atoi(ef) == 0);
+  const int fuse = ef ? atoi(ef) : 1;
+  const bool per_step_default = P.desc.model == BMPC_MODEL_HIGHWAY && P.desc.controller == BMPC_CTRL_ROBUST;
+  ch.fused_loop = (cvar || qp_loop) && !pl->psiref && fuse != 0 && (fuse == 2 || !per_step_default);
   return ch;
 }
 
@@ -1131,18 +1135,22 @@ int bmpc_loop_device(bmpc_plan* pl, const bmpc_env_desc* env, int t0, int nsteps
   const Plan& P = pl->hp.plan;
   if (P.desc.model != BMPC_MODEL_HIGHWAY || (P.desc.flags & BMPC_PLAN_TRANSFORM) || P.n != 4 || P.d != 2)
     return fail(-22, "bmpc_loop_device: the overtake scene needs a highway plan (n = 4, d = 2) without transform");
-  if (P.desc.controller != BMPC_CTRL_CVAR && P.desc.controller != BMPC_CTRL_ROBUST)
-    return fail(-22, "bmpc_loop_device: CVaR or robust controllers only");
+  const bool qp = P.desc.controller != BMPC_CTRL_CVAR;
+  if (qp && P.desc.controller != BMPC_CTRL_QP && P.desc.controller != BMPC_CTRL_ROBUST)
+    return fail(-22, "bmpc_loop_device: CVaR, BranchMPC (BMPC_CTRL_QP) or robust controllers only");
   if (nsteps < 1 || t0 < 0) return fail(-22, "bmpc_loop_device: nsteps >= 1 and t0 >= 0");
   if (env->n_lane < 1) return fail(-22, "bmpc_loop_device: n_lane < 1");
   if (const std::string e = check_script_covers(pl, t0, nsteps); !e.empty())
     return fail(-22, "bmpc_loop_device: " + e);
   return run_loop(
-      pl, true, false, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
+      pl, true, qp, t0, nsteps, d_scene, d_upred, d_x, d_z, d_xref, d_J, d_status, d_iters, stream,
       [&](int t) {
         return bmpc_env_step(pl, env, t, d_scene, d_upred, d_J, d_status, d_iters, d_x, d_z, d_xref, d_stats, stream);
       },
-      [&](const SolveLaunch& a) { return launch_loop_highway(a, *env, t0, nsteps, d_scene, d_stats); });
+      [&](const SolveLaunch& a) {
+        return qp ? launch_loop_highway_qp(a, *env, t0, nsteps, d_scene, d_stats)
+                  : launch_loop_highway(a, *env, t0, nsteps, d_scene, d_stats);
+      });
 }
 
 int bmpc_set_merge_scene(bmpc_plan* pl, const bmpc_merge_env_desc* desc, int nref, const double* grid,

@@ -185,7 +185,9 @@ enum {
   BMPC_KERNEL_IPM_BLK8 = 4,  /* k_solve_blk, one ego per 8-wave workgroup (small batches)  */
   BMPC_KERNEL_QP_RICH = 5,   /* k_qp (OSQP-class controllers), LDS-rich                    */
   BMPC_KERNEL_QP_LEAN = 6,   /* k_qp, lean                                                 */
-  BMPC_KERNEL_LOOP_RICH = 7, /* k_loop (bmpc_*loop_device): env + tree + IPM / QP steps per ego */
+  BMPC_KERNEL_LOOP_RICH = 7, /* k_loop (bmpc_*loop_device): env + tree + IPM / QP steps per ego --
+                                the CVaR IPM, or the QP solver for the quadruped scene's plans and the
+                                overtake scene's BranchMPC (and, on request, robust) plans */
   BMPC_KERNEL_LOOP_LEAN = 8  /* k_loop, lean                                                 */
 };
 
@@ -353,10 +355,16 @@ int bmpc_env_step(bmpc_plan* plan, const bmpc_env_desc* env, int t, double* d_sc
  * arguments and the same per-ego results, bit for bit.  The egos' loops are independent, so a
  * CVaR plan whose batch takes the one-wave IPM runs them in ONE launch (k_loop: each wave
  * steps its ego through all nsteps without a device-wide boundary between steps, so no step
- * waits for the slowest ego of the previous one); other batches run the two launches per step.
+ * waits for the slowest ego of the previous one); other CVaR batches run the two launches per
+ * step.  A BranchMPC plan (BMPC_CTRL_QP) runs ONE launch too, at any batch -- k_loop with the QP
+ * solver, BMPC_KERNEL_LOOP_RICH / _LEAN --; a robustMPC plan keeps its launches per step
+ * (BMPC_KERNEL_QP_RICH / _LEAN) unless BMPC_LOOP_FUSED=2 asks for that kernel.  BMPC_LOOP_FUSED
+ * (read on every call): 0 never fuses; unset or 1 the defaults above; 2 fuses every plan that
+ * has a k_loop, robust overtake plans included.
  * d_upred / d_J / d_status / d_iters hold the last solve's outputs on return (the next call's
- * t0 > 0 reads them); d_x / d_z / d_xref the last step's solve inputs.  Highway CVaR / robust
- * plans without transform (the scene's model); -22 otherwise.  An extension of the drop-in ABI
+ * t0 > 0 reads them); d_x / d_z / d_xref the last step's solve inputs.  Highway CVaR, BranchMPC
+ * (BMPC_CTRL_QP) and robust plans without transform (the scene's model); -22 otherwise
+ * (BMPC_CTRL_PROX: the reference never pairs it with this scene).  An extension of the drop-in ABI
  * for Monte-Carlo closed-loop batches (BASELINE config 5); the reference has no batched loop. */
 int bmpc_loop_device(bmpc_plan* plan, const bmpc_env_desc* env, int t0, int nsteps, double* d_scene,
                      double* d_upred, double* d_x, double* d_z, double* d_xref, double* d_J,
