@@ -113,6 +113,7 @@ _SIGS = {
     "bmpc_plan_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "bmpc_plan_destroy": (C.c_int, [C.c_void_p]),
     "bmpc_plan_info": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bmpc_last_lin_cache": (C.c_int, [C.c_void_p]),
     "bmpc_set_policies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bmpc_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bmpc_get_policies": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -544,6 +544,11 @@ class BatchPlan:
         g, v = (np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1)) for a in (grid, values))
         check(lib().bmpc_set_lane_ref(self._h, g.size, _p(g), _p(v)), "bmpc_set_lane_ref")
 
+    def last_lin_cache(self):
+        """Whether the solver kernel of the plan's last solve read A of the linearisation from its LDS
+        cache (bmpc_last_lin_cache)."""
+        return bool(lib().bmpc_last_lin_cache(self._h))
+
     def last_kernel(self):
         """The solver kernel the plan's last solve launched (abi.KERNEL_*, BMPC_INFO_SOLVER)."""
         info = np.zeros(abi.INFO_COUNT, np.int32)

@@ -39,6 +39,17 @@
 #define BMPC_ITER_RECORD 1
 #endif
 #define BMPC_ITER_LDS 32   // doubles of LDS the record takes (IterRec's slots, rounded up)
+// BMPC_LIN_LDS: the one-wave IPM reads A of the solve's linearisation -- the input nodes' state
+// matrices, written once per solve by the tree step and never by the IPM -- through an accessor
+// (bmpc_ipm.h, lin_A) over a compact copy in the wave's LDS instead of re-reading the dense slab
+// array in every pass of every iteration.  A model describes which entries of A vary from node to
+// node (bmpc_model.h, HighwayLin); only those are stored (Plan::lds_lin, filled and checked against
+// the slab at the start of each solve by lin_fill), the others are the model's constants.  Every
+// term of every sum stays where it was, so the values are the parent's.  0: the parent's slab reads
+// everywhere.  The host build follows the same default.
+#ifndef BMPC_LIN_LDS
+#define BMPC_LIN_LDS 1
+#endif
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define BMPC_HD __host__ __device__ __forceinline__
@@ -124,8 +135,10 @@ struct TopoT {
   BMPC_TOPO_FIELDS(BMPC_TOPO_MEMBER_)
 };
 // the tables in global memory (k_tree) and the per-wave LDS copy (k_ipm / k_qp: every
-// topology lookup on the solver's dependent chains is an LDS read, not a memory round trip)
+// topology lookup on the solver's dependent chains is an LDS read, not a memory round trip; the
+// launches with the linearisation cache, BMPC_LIN_LDS, hold the copy in 16 bits to make its room)
 typedef const BMPC_AS_LDS int32_t lint;
+typedef const BMPC_AS_LDS int16_t lint16;
 typedef TopoT<gint*> Topo;
 typedef TopoT<lint*> TopoL;
 
@@ -144,6 +157,22 @@ enum { XF_S = 0, XF_BX = BMPC_MAX_N * BMPC_MAX_N, XF_SON = XF_BX + BMPC_MAX_FX, 
 // without S (or for the other models) the plan's Fx, W1, QQ, bx are read directly.
 enum { ECO_FX = 0, ECO_W1 = BMPC_MAX_FX * BMPC_MAX_N, ECO_QQ = ECO_W1 + BMPC_MAX_N * BMPC_MAX_N,
        ECO_BX = ECO_QQ + BMPC_MAX_N * BMPC_MAX_N, ECO_COUNT = ECO_BX + BMPC_MAX_FX };
+
+// A model's A as the IPM's accessor sees it at run time (executors without a compile-time
+// description: the host build): per entry the cache slot or -1, and the constant it then equals.
+// Filled at plan build from the model's compile-time description (bmpc_model.h), which the
+// one-wave kernels read directly.
+struct LinDesc {
+  int na;   // entries of A that vary from node to node (0: the model has no description)
+  signed char a_slot[BMPC_MAX_N * BMPC_MAX_N];
+  double a_const[BMPC_MAX_N * BMPC_MAX_N];
+};
+// the description of a model without one
+struct NoLin {
+  static constexpr int NA = 0;
+  static constexpr int a_slot(int, int) { return -1; }
+  static constexpr double a_const(int, int) { return 0.0; }
+};
 
 struct Plan {
   bmpc_plan_desc desc;
@@ -169,6 +198,15 @@ struct Plan {
   int nlds_lean;            // LDS doubles when the coupling system lives in the slab (Layout::coup)
   int lds_scr, nscr;       // tree-solve LDS scratch (slack terms of the pre-pass; 0 = none)
   int lds_it;              // the IPM's iteration record (BMPC_ITER_LDS doubles; before lds_piv: lean launches have it)
+  // the solve's linearisation cache (BMPC_LIN_LDS): the varying entries of A, [entry][input node],
+  // nlin_a doubles behind the other doubles of a launch that reads it -- at nlds_rich in a rich
+  // launch, at nlds_lean in a lean one (bmpc_ipm.h lin_off); a launch that does not read it has no
+  // such area (bmpc_dev.h solver_lds_bytes).  0: it did not fit the 16-egos-per-CU budget (or the
+  // model has no description) and the IPM reads A from the slab.  nlds = nlds_rich + nlin_a: what
+  // the host build's LDS stand-in holds.
+  int nlds_rich, nlin_a;
+  int tab16;               // every table value fits 16 bits (a plan with the cache: its launches' LDS copy is 16-bit)
+  LinDesc lin;
   int cgrp;  // lanes per cone group (power of two, cgrp * ceil(ncones / ngrp) covers all cones)
   int maxq;   // largest cone dimension (fused cone passes hold a cone's rows in registers when
               // maxq <= X::kConeRegRows * cgrp)

@@ -39,13 +39,19 @@ namespace dev {
 constexpr bool kDppWave = BMPC_DPP_REDUCE == 2;                              // DevExecT (k_ipm, k_qp, k_tree)
 constexpr bool kDppBlock = BMPC_DPP_REDUCE == 1 || BMPC_DPP_REDUCE == 2;     // DevBlockExecT (k_solve_blk)
 
-template <bool TR, bool TL = true>
+// LA, LN: the IPM reads A of the solve's linearisation from the wave's LDS cache (bmpc_ipm.h
+// lin_A), through the model's description LN of it -- the launch's choice, like TL (bmpc_hip.hip
+// choose_launch).  k_tree, k_qp and the tools' kernels take the defaults.
+template <bool TR, bool TL = true, bool LA = false, class LN = NoLin>
 struct DevExecT {
   static constexpr bool kTransform = TR;   // per-ego S / bx constants in LDS (merge plans)
+  static constexpr bool kLinA = LA;
+  using Lin = LN;
   // LDS-rich launch (TL): topology tables copied to LDS and the coupling system in LDS;
   // lean launch: tables read from the plan's blob, coupling system in the slab
   static constexpr bool kCoupLds = TL;
-  using tab_ptr = typename std::conditional<TL, lint*, gint*>::type;
+  // (with the cache the LDS copy of the tables is 16-bit: what makes its room at 16 egos per CU)
+  using tab_ptr = typename std::conditional<TL, typename std::conditional<LA, lint16*, lint*>::type, gint*>::type;
   int lane;
   ldouble* lds;  // this wave's LDS scratch (Plan::nlds doubles; k_ipm / k_qp only)
   tab_ptr tab;   // topology tables (k_ipm / k_qp only)
@@ -105,6 +111,12 @@ struct DevExecT {
 };
 
 using DevExec = DevExecT<false>;
+// the IPM's one-wave executor of model M, with the cache or without (then the default executor's type)
+template <class M, bool TL, bool LA>
+using IpmExecT = DevExecT<M::kTransform, TL, LA, typename std::conditional<LA, typename M::Lin, NoLin>::type>;
+// a model's launches are compiled with the cache where it has a description
+template <class M>
+constexpr bool kHasLin = BMPC_LIN_LDS && M::Lin::NA > 0;
 
 #ifndef BMPC_BLK_RED2
 #define BMPC_BLK_RED2 1   // whole-executor reductions with one barrier (two buffers in turn)
@@ -134,6 +146,8 @@ struct DevBlockExecT {
   static constexpr int kConeBatch = NW == 4 ? 2 : 4;
   static constexpr int kRedMax = 16;
   static constexpr bool kIterRecord = false;   // the IPM loop with its state in locals (bmpc_ipm.h, ipm_solve)
+  static constexpr bool kLinA = false;   // A from the slab -- or from its LDS-resident span (k_solve_blk)
+  using Lin = NoLin;
   __device__ double tsum(double v) const {
     v += dpp_d<0xB1>(v);
     v += dpp_d<0x4E>(v);
@@ -198,28 +212,32 @@ struct Bundle {
   Layout L;
 };
 
-// Dynamic LDS of the solver kernels: Plan::nlds doubles of scratch, then a copy of the
-// topology tables (Plan::ntab int32), then (transform-capable models) ECO_COUNT doubles of
+// Dynamic LDS of the solver kernels: Plan::nlds_rich / nlds_lean doubles of scratch, then a copy of the
+// topology tables (Plan::ntab int32; tab16: of 16 bits, the launches with the linearisation cache), then
+// (transform-capable models) ECO_COUNT doubles of
 // per-ego constants.  The table copy is one batched pass at kernel start; every later tree /
 // cone / node-index lookup of the solve is an LDS read.
-__host__ __device__ inline size_t solver_lds_bytes(const Plan& P, bool transform, bool rich) {
-  const size_t tab = rich ? (sizeof(int32_t) * (size_t)P.ntab + 7) & ~(size_t)7 : 0;
-  return sizeof(double) * (size_t)(rich ? P.nlds : P.nlds_lean) + tab + (transform ? sizeof(double) * ECO_COUNT : 0);
+// lin: a launch that reads the linearisation cache -- Plan::nlin_a doubles behind the others, its table copy 16-bit
+__host__ __device__ inline size_t solver_lds_bytes(const Plan& P, bool transform, bool rich, bool lin = false) {
+  const size_t tab = rich ? ((lin ? sizeof(int16_t) : sizeof(int32_t)) * (size_t)P.ntab + 7) & ~(size_t)7 : 0;
+  return sizeof(double) * (size_t)((rich ? P.nlds_rich : P.nlds_lean) + (lin ? P.nlin_a : 0)) + tab +
+         (transform ? sizeof(double) * ECO_COUNT : 0);
 }
-template <bool TR, bool TL>
-__device__ __forceinline__ DevExecT<TR, TL> solver_exec(const Plan& P, double* lds_dyn) {
+template <bool TR, bool TL, bool LA = false, class LN = NoLin>
+__device__ __forceinline__ DevExecT<TR, TL, LA, LN> solver_exec(const Plan& P, double* lds_dyn) {
   const int32_t* gtab = (const int32_t*)P.t.br_depth;   // blob base (the first table)
-  double* eco = lds_dyn + (solver_lds_bytes(P, false, TL) / sizeof(double));
+  double* eco = lds_dyn + (solver_lds_bytes(P, false, TL, LA) / sizeof(double));
   // W1 | Wu | Fx | Fu for the IPM passes' per-lane row lookups
   for (int i = threadIdx.x; i < P.nconst; i += 64) lds_dyn[P.lds_w + i] = plan_const(P, i);
   if constexpr (TL) {
-    int32_t* tabl = reinterpret_cast<int32_t*>(lds_dyn + P.nlds);
-    for (int i = threadIdx.x; i < P.ntab; i += 64) tabl[i] = gtab[i];
+    using TT = typename std::conditional<LA, int16_t, int32_t>::type;
+    TT* tabl = reinterpret_cast<TT*>(lds_dyn + P.nlds_rich + (LA ? P.nlin_a : 0));
+    for (int i = threadIdx.x; i < P.ntab; i += 64) tabl[i] = (TT)gtab[i];   // (16 bits: in range, Plan::tab16)
     __syncthreads();
-    return DevExecT<TR, TL>{(int)threadIdx.x, (ldouble*)lds_dyn, (lint*)tabl, (ldouble*)eco};
+    return DevExecT<TR, TL, LA, LN>{(int)threadIdx.x, (ldouble*)lds_dyn, (const BMPC_AS_LDS TT*)tabl, (ldouble*)eco};
   } else {
     __syncthreads();
-    return DevExecT<TR, TL>{(int)threadIdx.x, (ldouble*)lds_dyn, (gint*)gtab, (ldouble*)eco};
+    return DevExecT<TR, TL, LA, LN>{(int)threadIdx.x, (ldouble*)lds_dyn, (gint*)gtab, (ldouble*)eco};
   }
 }
 
@@ -241,7 +259,7 @@ __device__ __forceinline__ DevBlockExecT<TR, true, NW> solver_exec_blk(const Pla
   const int t = threadIdx.x, nt = 64 * NW;
   for (int i = t; i < P.nconst; i += nt) lds_dyn[P.lds_w + i] = plan_const(P, i);
   const int32_t* gtab = (const int32_t*)P.t.br_depth;
-  int32_t* tabl = reinterpret_cast<int32_t*>(lds_dyn + P.nlds);
+  int32_t* tabl = reinterpret_cast<int32_t*>(lds_dyn + P.nlds_rich);
   for (int i = t; i < P.ntab; i += nt) tabl[i] = gtab[i];
   double* eco = lds_dyn + (solver_lds_bytes(P, false, true) / sizeof(double));
   double* red = lds_dyn + ((solver_lds_bytes(P, TR, true) + 7) & ~(size_t)7) / sizeof(double);
@@ -370,7 +388,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE > 1 ? WP
   tree_step<DevExec, M>(ex, P, L, E, x + e * P.n, z + e * P.n, xref + e * P.n);
 }
 
-template <class M, bool TL>
+template <class M, bool TL, bool LA = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) void k_ipm(const Bundle* __restrict__ B, double* __restrict__ ws,
                                             const bmpc_policy* __restrict__ pol, double* upred,
                                             double* xpred, double* bw, double* J, int32_t* status,
@@ -380,9 +398,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const Plan& P = B->P;
   const Layout& L = B->L;
   extern __shared__ double lds_dyn[];
-  const auto ex = solver_exec<M::kTransform, TL>(P, lds_dyn);
+  using X = IpmExecT<M, TL, LA>;
+  const auto ex = solver_exec<M::kTransform, TL, LA, typename X::Lin>(P, lds_dyn);
   EgoView E{ws + L.stride * (size_t)e, pol + (size_t)e * P.m};
-  IpmResult r = solve_ego_ipm<DevExecT<M::kTransform, TL>, M>(ex, P, L, E);
+  IpmResult r = solve_ego_ipm<X, M>(ex, P, L, E);
   write_outputs<64>(P, L, E.ws, e, E.ws + L.sol + P.oJ, r, upred, xpred, bw, J, status, iters);
 }
 
@@ -598,7 +617,7 @@ struct QuadScene {
 #ifndef BMPC_LOOP_RECORD_TEMPLATE
 #define BMPC_LOOP_RECORD_TEMPLATE 0
 #endif
-template <class M, bool TL, class SC, bool REC>
+template <class M, bool TL, class SC, bool REC, bool LA = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) void k_loop(
     const Bundle* __restrict__ B, double* __restrict__ ws, bmpc_policy* __restrict__ pol, SC sc, int t0,
     int nsteps, double* scene, double* upred, double* xs, double* zs, double* xrefs, double* J, int32_t* status,
@@ -609,7 +628,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
   const Layout& L = B->L;
   extern __shared__ double lds_dyn[];
   constexpr bool TR = SC::kQp ? false : M::kTransform;   // (k_qp's executor takes no transform)
-  const auto ex = solver_exec<TR, TL>(P, lds_dyn);
+  using X = typename std::conditional<SC::kQp, DevExecT<false, TL>, IpmExecT<M, TL, LA>>::type;
+  const auto ex = solver_exec<TR, TL, X::kLinA, typename X::Lin>(P, lds_dyn);
   bmpc_policy* pe = pol + (size_t)e * P.m;
   EgoView E{ws + L.stride * (size_t)e, pe};
   double* st = scene + (size_t)e * ENV_STRIDE;
@@ -624,7 +644,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BMPC_WPE))) 
       sc.step(P, L, t, st, pe, E.ws, up, x, z, xr, J[e], status[e], iters[e],
               stats ? stats + (size_t)e * ENVS_STRIDE : nullptr);
     __syncthreads();
-    using X = DevExecT<TR, TL>;
     loop_tree_step<X, M>(ex, P, L, E, x, z, xr);   // k_tree
     IpmResult r;   // k_ipm / k_qp
     if constexpr (SC::kQp) {
@@ -683,6 +702,7 @@ struct SolveLaunch {
   bmpc_loop_record rec = {};         // the fused closed loop's recorder (capacity 0: none)
   bmpc_obstacle_sampling smp = {};   // the fused closed loop's obstacle sampler (mode 0: none)
   const SceneOptions* opt = nullptr;   // ... and the plan's device block of scene options (null: none)
+  bool lin = false;  // the IPM reads A from its LDS cache (choose_launch: the plan carved it)
 };
 using LaunchFn = hipError_t(const SolveLaunch&);
 
@@ -726,6 +746,12 @@ hipError_t launch_solver(const SolveLaunch& a) {
     if (atoi(e) == 1)
       return launch_solver_kernel(k_ipm_w2<M>, a, 128, solver_lds_bytes_blk(*a.hplan, M::kTransform, 2));
 #endif
+  if constexpr (kHasLin<M>) {
+    if (a.lin)
+      return a.rich ? launch_solver_kernel(k_ipm<M, true, true>, a, 64, a.lds_bytes)
+                    : launch_solver_kernel(k_ipm<M, false, true>, a, 64, a.lds_bytes);
+  }
+  if (a.lin) return hipErrorInvalidValue;   // (no kernel of this model reads the cache the plan carved)
   return a.rich ? launch_solver_kernel(k_ipm<M, true>, a, 64, a.lds_bytes)
                 : launch_solver_kernel(k_ipm<M, false>, a, 64, a.lds_bytes);
 }
@@ -738,6 +764,12 @@ hipError_t launch_loop(const SolveLaunch& a, const SC& sc, int t0, int nsteps, d
       a.rich ? k_loop<M, true, SC, true> : k_loop<M, false, SC, true>;
   if constexpr (BMPC_LOOP_RECORD_TEMPLATE != 0) {
     if (a.rec.capacity < 1) k = a.rich ? k_loop<M, true, SC, false> : k_loop<M, false, SC, false>;
+  }
+  if constexpr (!SC::kQp) {   // the IPM with its linearisation cache, as launch_solver
+    if constexpr (kHasLin<M>) {
+      if (a.lin) k = a.rich ? k_loop<M, true, SC, true, true> : k_loop<M, false, SC, true, true>;
+    }
+    if (a.lin && !kHasLin<M>) return hipErrorInvalidValue;
   }
   const hipError_t e = optin_lds((const void*)k, a.lds_bytes);
   if (e != hipSuccess) return e;

@@ -27,13 +27,14 @@ namespace {
 // waves per SIMD).  Deep trees (N=30, NB=2: 17 KB of tables, a 20 KB coupling matrix) run
 // lean, 16 egos per CU instead of 4, unless the batch is resident either way.  BMPC_LDS_RICH=0/1
 // forces either.
-static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, size_t lds_per_cu) {
+// lin: the launch reads the linearisation cache (choose_launch): priced with it.
+static bool choose_lds_rich(const Plan& P, bool transform, int batch, int cus, size_t lds_per_cu, bool lin) {
   if (const char* e = getenv("BMPC_LDS_RICH")) return atoi(e) != 0;
   auto egos = [&](size_t b) { return std::min<size_t>(16, lds_per_cu / std::max<size_t>(b, 1)); };
-  const size_t rich = egos(solver_lds_bytes(P, transform, true));
+  const size_t rich = egos(solver_lds_bytes(P, transform, true, lin));
   // a batch that is resident either way (one CU per `rich` egos) runs rich: residency is not
   // what limits it
-  return (size_t)batch <= (size_t)cus * rich || rich >= egos(solver_lds_bytes(P, transform, false));
+  return (size_t)batch <= (size_t)cus * rich || rich >= egos(solver_lds_bytes(P, transform, false, lin));
 }
 
 // one thread per ego: the closed-loop scene step (bmpc_env.h) around the solve.  smp: the plan's
@@ -531,6 +532,7 @@ struct bmpc_plan {
   int t_cnt = 0;
   bool pol_on_device = false;   // bmpc_env_step re-targeted d_pol: h_pol is stale
   int last_kernel = BMPC_KERNEL_NONE;   // solver kernel of the last launch (BMPC_INFO_SOLVER)
+  bool last_lin = false;                // ... and whether it read the linearisation cache (bmpc_last_lin_cache)
   double* d_lref = nullptr;   // lane reference of the *_PSIREF policies (grid | values)
   // small-batch kernel: per-ego layouts with LDS-resident spans (blk_layouts), built on the first
   // small-batch solve for this plan's LDS base
@@ -622,6 +624,7 @@ extern "C" {
 
 const char* bmpc_last_error(void) { return g_err.c_str(); }
 int bmpc_abi_version(void) { return BMPC_ABI_VERSION; }
+int bmpc_last_lin_cache(const bmpc_plan* pl) { return pl && pl->last_lin ? 1 : 0; }
 
 int bmpc_open(int hip_device, bmpc_ctx** out) {
   if (!out) return fail(-22, "null output pointer");
@@ -909,6 +912,7 @@ static int blk_layouts(bmpc_plan* pl, size_t lds_base) {
 struct LaunchChoice {
   int nw;             // small-batch launch (k_solve_blk): waves per ego; 0: one wave per ego
   bool rich;          // LDS-rich or lean (choose_lds_rich; the small-batch kernel is rich)
+  bool lin;           // the one-wave IPM reads A from its LDS cache (bmpc_ipm.h lin_A; the plan carved it)
   size_t lds_bytes;   // dynamic LDS of the solver kernel (before the small-batch kernel's spans)
   bool blk_lds;       // small-batch launch: the IPM's arrays in LDS (blk_layouts)
   bool fused_loop;    // a closed loop runs as one k_loop launch instead of launches per step
@@ -942,8 +946,15 @@ static LaunchChoice choose_launch(const bmpc_plan* pl, bool xform, bool qp_loop 
     ch.blk_lds = !(el && atoi(el) == 0);
     return ch;
   }
-  ch.rich = choose_lds_rich(P, xform, pl->batch, c->cus, c->lds_per_cu);
-  ch.lds_bytes = solver_lds_bytes(P, xform, ch.rich);
+  // The IPM with its linearisation cache (A from LDS, 16-bit table copy), where the plan carved one,
+  // for batches beyond 8 egos per CU, as k_tree's register budget (launch_tree): those are bound by
+  // the bytes the cache saves; smaller ones by latency, where the cache's selects and the narrow
+  // table loads cost more than the slab reads they replace (1,024 egos +1.2%).
+  // BMPC_LIN_CACHE=0/1 forces either.
+  ch.lin = BMPC_LIN_LDS && cvar && P.nlin_a > 0 && pl->batch > 8 * c->cus;
+  if (const char* e = getenv("BMPC_LIN_CACHE")) ch.lin = BMPC_LIN_LDS && cvar && P.nlin_a > 0 && atoi(e) != 0;
+  ch.rich = choose_lds_rich(P, xform, pl->batch, c->cus, c->lds_per_cu, ch.lin);
+  ch.lds_bytes = solver_lds_bytes(P, xform, ch.rich, ch.lin);
   // occupancy experiments: BMPC_IPM_LDS_BYTES reserves at least that much LDS per workgroup
   // (fewer egos resident per CU => a smaller working set in L2 / Infinity Cache)
   if (const char* e = getenv("BMPC_IPM_LDS_BYTES")) {
@@ -964,6 +975,7 @@ static SolveLaunch solve_launch(const bmpc_plan* pl, const LaunchChoice& ch, hip
   SolveLaunch a{pl->d_bundle, pl->d_ws, pl->d_pol, d_x, d_z, d_xref, d_upred, d_xpred, d_bw, d_J, d_status,
                 d_iters, pl->batch, ch.lds_bytes, ch.rich, pl->hp.plan.desc.controller != BMPC_CTRL_CVAR, s};
   if (ch.nw) a.nw = ch.nw;
+  a.lin = ch.lin;
   a.cus = pl->ctx->cus;
   a.hplan = &pl->hp.plan;
   return a;
@@ -1011,6 +1023,7 @@ static int launch_solve(bmpc_plan* pl, const double* d_x, const double* d_z, con
     }
   }
   pl->ph.fill(a, !ch.nw && !a.qp && ch.rich, solver, ml.phased);
+  pl->last_lin = a.lin && !a.qp;
   pl->last_kernel = ch.nw   ? (ch.nw == 8 ? BMPC_KERNEL_IPM_BLK8 : BMPC_KERNEL_IPM_BLK4)
                     : a.qp  ? (ch.rich ? BMPC_KERNEL_QP_RICH : BMPC_KERNEL_QP_LEAN)
                             : (ch.rich ? BMPC_KERNEL_IPM_RICH : BMPC_KERNEL_IPM_LEAN);
@@ -1056,6 +1069,7 @@ static int run_loop(bmpc_plan* pl, bool retargets, bool qp_loop, int t0, int nst
   a.rec = pl->rec;
   a.smp = pl->smp;
   a.opt = scene_options(pl);
+  pl->last_lin = a.lin && !qp_loop;
   pl->last_kernel = ch.rich ? BMPC_KERNEL_LOOP_RICH : BMPC_KERNEL_LOOP_LEAN;
   // (the whole fused launch is booked as the solver's time, none as the tree's)
   if (const int rc = timing_mark(pl, s, 0)) return rc;

@@ -143,6 +143,84 @@ struct Ctx {
   BMPC_HD Ctx uniform() const { return Ctx{uniform_ptr(P), uniform_ptr(L), uniform_ptr(ws)}; }
 };
 
+// ------------------------------------------------------------------------------------
+// A of the solve's linearisation behind an accessor (BMPC_LIN_LDS, bmpc_core.h).  The tree step
+// writes the input nodes' A to the slab once per solve and the IPM only reads it -- in the
+// residuals, the Riccati recursion and both sweeps of every tree solve, each pass a fetch of its
+// own.  Where the executor has the cache, an entry that varies from node to node is a
+// load from the wave's LDS ([entry][node]: lanes that walk the nodes read consecutive doubles) and
+// every other entry is the model's constant; lin_fill loads the cache at the start of the solve
+// and checks each constant against the slab.  The callers keep every term of their sums, so a
+// value is formed from the same operands in the same order as with the slab reads.
+//
+// Whether an executor reads the cache: the one-wave kernels declare kLinA and their model's
+// description Lin -- compile-time properties chosen with the launch, as rich / lean is
+// (bmpc_hip.hip, choose_launch); an executor that declares nothing (the host build) follows the
+// plan through its run-time copy of the description (Plan::lin).
+// ------------------------------------------------------------------------------------
+template <class X, class = void>
+struct lin_exec {
+  static constexpr bool kStatic = false;
+};
+template <class X>
+struct lin_exec<X, decltype((void)X::kLinA)> {
+  static constexpr bool kStatic = true;
+};
+template <class X, bool ST = lin_exec<X>::kStatic>
+struct LinView {   // the plan's description
+  CPlan* P;
+  BMPC_HD bool a_on() const { return BMPC_LIN_LDS && P->nlin_a > 0; }
+  BMPC_HD int a_slot(int i, int j) const { return P->lin.a_slot[i * P->n + j]; }
+  BMPC_HD double a_const(int i, int j) const { return P->lin.a_const[i * P->n + j]; }
+};
+template <class X>
+struct LinView<X, true> {   // the executor's
+  CPlan* P;
+  BMPC_HD bool a_on() const { return BMPC_LIN_LDS && X::kLinA; }
+  BMPC_HD int a_slot(int i, int j) const { return X::Lin::a_slot(i, j); }
+  BMPC_HD double a_const(int i, int j) const { return X::Lin::a_const(i, j); }
+};
+
+// where the cache lies in the executor's LDS: behind the launch's other doubles (Plan::nlin_a)
+template <class X>
+BMPC_HD int lin_off(CPlan& P) {
+  return X::kCoupLds ? P.nlds_rich : P.nlds_lean;
+}
+
+// A_u(i, j); Ad: the slab's array
+template <class X, int NX>
+BMPC_HD double lin_A(const X& ex, CPlan& P, const gdouble* Ad, int u, int i, int j) {
+  const LinView<X> V{&P};
+  if (V.a_on()) {
+    const int s = V.a_slot(i, j);
+    const double v = ex.lds[lin_off<X>(P) + (s < 0 ? 0 : s) * P.U + u];   // (unconditional: a select, no branch)
+    return s < 0 ? V.a_const(i, j) : v;
+  }
+  return Ad[u * NX * NX + i * NX + j];
+}
+
+// The cache of this solve: A's varying entries out of the slab into LDS, every other entry compared
+// with its constant (==, so a zero of either sign passes).  False if one differs -- the model's
+// description does not hold for this slab -- and the solve must not run.
+template <class X, int NX>
+BMPC_HD bool lin_fill(const X& ex, CPlan& P, CLayout& L, const gdouble* ws) {
+  const LinView<X> V{&P};
+  if (!V.a_on()) return true;
+  const gdouble* Ad = ws + L.Ad;
+  auto* ca = ex.lds + lin_off<X>(P);
+  double bad = 0.0;
+  for (int it = ex.lane; it < P.U * NX * NX; it += ex.nlanes) {
+    const int u = it / (NX * NX), i = it % (NX * NX) / NX, j = it % NX;
+    const double v = Ad[it];
+    const int s = V.a_slot(i, j);
+    if (s >= 0) ca[s * P.U + u] = v;
+    else bad += v == V.a_const(i, j) ? 0.0 : 1.0;
+  }
+  const bool ok = ex.uniform(!(ex.sum(bad) > 0.0));
+  ex.sync();
+  return ok;
+}
+
 // xRef' Q (the cone rows' linear cost term, MPC_branch.py:1927-1940); xref is written by the
 // tree kernel, Q is plan constant
 template <int NX>
@@ -810,7 +888,7 @@ BMPC_HD void apply_A(const X ex, const Ctx& C, const gdouble* zv, gdouble* out) 
 #pragma unroll
       for (int r = 0; r < NX; ++r) {
 #pragma unroll
-        for (int s2 = 0; s2 < NX; ++s2) o.v[r] -= Ad[su * NX * NX + r * NX + s2] * xs[s2];
+        for (int s2 = 0; s2 < NX; ++s2) o.v[r] -= lin_A<X, NX>(ex, P, Ad, su, r, s2) * xs[s2];
 #pragma unroll
         for (int s2 = 0; s2 < NU; ++s2) o.v[r] -= Bd[su * NX * NU + r * NU + s2] * us[s2];
       }
@@ -856,7 +934,7 @@ BMPC_HD void apply_AT(const X ex, const Ctx& C, const gdouble* y, gdouble* out) 
       for (int s2 = 0; s2 < NX; ++s2) {
         double v = 0.0;
 #pragma unroll
-        for (int r = 0; r < NX; ++r) v += Ad[u * NX * NX + r * NX + s2] * ys[r];
+        for (int r = 0; r < NX; ++r) v += lin_A<X, NX>(ex, P, Ad, u, r, s2) * ys[r];
         ax[s2] -= v;
       }
 #pragma unroll
@@ -1788,9 +1866,9 @@ BMPC_FN bool kkt_factor(const X ex, const Ctx Cin, bool zero_g) {
 #pragma unroll
           for (int j = 0; j < NX; ++j) Hx[q][j] = ws[L.hx + k * NX * NX + i * NX + j];
 #pragma unroll
-          for (int j = 0; j < NX; ++j) Ar[q][j] = Ad[u * NX * NX + i * NX + j];
+          for (int j = 0; j < NX; ++j) Ar[q][j] = lin_A<X, NX>(ex, P, Ad, u, i, j);
 #pragma unroll
-          for (int j = 0; j < NX; ++j) Ac[q][j] = Ad[u * NX * NX + j * NX + i];   // column i
+          for (int j = 0; j < NX; ++j) Ac[q][j] = lin_A<X, NX>(ex, P, Ad, u, j, i);   // column i
 #pragma unroll
           for (int m = 0; m < NU; ++m) Br[q][m] = Bd[u * NX * NU + i * NU + m];
         }
@@ -2202,7 +2280,7 @@ BMPC_FN_TREE_SOLVE void tree_solve(const X ex, const Ctx Cin, int nr, const gdou
           const int i = gl * RX + q < NX ? gl * RX + q : NX - 1;
           qx[q] = pre ? q0[k * NX + i] : qx0(rr, k, i);
 #pragma unroll
-          for (int j = 0; j < NX; ++j) Acol[q][j] = ws[L.Ad + u * NX * NX + j * NX + i];
+          for (int j = 0; j < NX; ++j) Acol[q][j] = lin_A<X, NX>(ex, P, ws + L.Ad, u, j, i);
 #pragma unroll
           for (int m = 0; m < NU; ++m) Brow[q][m] = ws[L.Bd + u * NX * NU + i * NU + m];
 #pragma unroll
@@ -2292,7 +2370,7 @@ BMPC_FN_TREE_SOLVE void tree_solve(const X ex, const Ctx Cin, int nr, const gdou
         for (int q = 0; q < RX; ++q) {
           const int i = gl * RX + q < NX ? gl * RX + q : NX - 1;
 #pragma unroll
-          for (int j = 0; j < NX; ++j) Arow[q][j] = ws[L.Ad + u * NX * NX + i * NX + j];
+          for (int j = 0; j < NX; ++j) Arow[q][j] = lin_A<X, NX>(ex, P, ws + L.Ad, u, i, j);
 #pragma unroll
           for (int m = 0; m < NU; ++m) Brow[q][m] = ws[L.Bd + u * NX * NU + i * NU + m];
 #pragma unroll

@@ -241,9 +241,21 @@ BMPC_HD S lref_eval(const LaneRef& R, const S& t) {
 // ------------------------------------------------------------------------------------
 // Highway: x = (X, Y, v, psi), u = (a, r)           highway_branch_dyn.py:17-398
 // ------------------------------------------------------------------------------------
+// What of the highway models' A varies from node to node (BMPC_LIN_LDS, bmpc_core.h; read by
+// bmpc_ipm.h's lin_A and checked against every solve's slab by lin_fill).  With f = (v cos psi,
+// v sin psi, a, r), A = I + dt df/dx differs from the identity at (0,2), (0,3), (1,2), (1,3) alone.
+// (B is dt at (2,0), (3,1) and 0 elsewhere, and without the state transformation dh's columns 2
+// and 3 are 0; reading those as constants too measured under the bar to keep)
+struct HighwayLin {
+  static constexpr int NA = 4;
+  static constexpr int a_slot(int i, int j) { return i < 2 && j >= 2 ? i * 2 + (j - 2) : -1; }
+  static constexpr double a_const(int i, int j) { return i == j ? 1.0 : 0.0; }
+};
+
 struct Highway {
   static constexpr int NX = 4, NU = 2;
   static constexpr bool kTransform = false;   // no per-ego S / bx (see HighwayMerge)
+  using Lin = HighwayLin;   // (HighwayMerge and HighwayT inherit it)
 
   template <class S, class T>
   BMPC_HD static void f(const S* x, const T* u, S* xd) {  // dubin (:17-34)
@@ -418,6 +430,7 @@ struct HighwayT : Highway {
 struct Quadruped {
   static constexpr int NX = 3, NU = 3;
   static constexpr bool kTransform = false;
+  using Lin = NoLin;
 
   template <class S, class T>
   BMPC_HD static void f(const S* x, const T* u, S* xd) {  // quad_kinetics (:14-27)

@@ -1,6 +1,7 @@
 // bmpc_plan.cpp -- host-side plan construction (see bmpc_plan.h).
 #include <stdlib.h>
 #include "bmpc_plan.h"
+#include "bmpc_model.h"
 
 #include <algorithm>
 
@@ -82,6 +83,22 @@ void weight_root(const double* M, int n, double* W) {
   } else {
     sqrtm_sym(M, n, W);
   }
+}
+
+// the run-time form of a model's compile-time description of its linearisation (bmpc_model.h)
+template <class Ln>
+void lin_describe_as(int n, LinDesc& D) {
+  D.na = Ln::NA;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      D.a_slot[i * n + j] = (signed char)Ln::a_slot(i, j);
+      D.a_const[i * n + j] = Ln::a_const(i, j);
+    }
+}
+void lin_describe(const bmpc_plan_desc& desc, LinDesc& D) {
+  if (desc.model == BMPC_MODEL_HIGHWAY) lin_describe_as<Highway::Lin>(desc.n, D);   // (HighwayT's too)
+  else if (desc.model == BMPC_MODEL_HIGHWAY_MERGE) lin_describe_as<HighwayMerge::Lin>(desc.n, D);
+  else lin_describe_as<Quadruped::Lin>(desc.n, D);
 }
 
 }  // namespace
@@ -307,6 +324,23 @@ std::string build_plan(const bmpc_plan_desc& desc, HostPlan& hp) {
     P.ng = 0;
     P.nsm = 0;
   }
+  // ---- concatenated tables -------------------------------------------------------------------
+#define BMPC_TOPO_HOSTVEC_(n) &hp.n,
+  std::vector<int32_t>* tabs[] = {BMPC_TOPO_FIELDS(BMPC_TOPO_HOSTVEC_)};   // same order as Topo
+#undef BMPC_TOPO_HOSTVEC_
+  hp.blob.clear();
+  hp.blob_off.clear();
+  for (auto* v : tabs) {
+    hp.blob_off.push_back(hp.blob.size());
+    hp.blob.insert(hp.blob.end(), v->begin(), v->end());
+  }
+  hp.point_tables(hp.blob.data());
+  // the launches with the linearisation cache hold their LDS copy of the blob in 16 bits: a plan
+  // with a value outside that range gets no cache
+  P.tab16 = 1;
+  for (int32_t v : hp.blob)
+    if (v < INT16_MIN || v > INT16_MAX) P.tab16 = 0;
+
   // LDS of the solver kernels (doubles): a 64-double reduction area, the tree-solve scratch
   // (CVaR IPM: the pre-pass slack terms, T * Nc doubles, while the whole stays within 9,984
   // bytes = 16 egos per CU), then the dense coupling system (matrix, pivots, rhs).  A lean-LDS
@@ -338,9 +372,26 @@ std::string build_plan(const bmpc_plan_desc& desc, HostPlan& hp) {
   P.lds_rhs = P.lds_piv + P.nsm;
   P.lds_rhs2 = P.lds_rhs + P.nsm;   // the pair's second right-hand side (kkt_back_pair)
   P.lds_M = P.lds_rhs2 + P.nsm;
-  P.nlds = P.lds_M + P.nsm * P.nsm;
+  P.nlds_rich = P.lds_M + P.nsm * P.nsm;
   P.nlds_lean = P.lds_M;
-  if (P.nscr > 0 && P.nlds > 1248) return "internal: the tree-solve LDS staging overflows the 16-egos-per-CU budget";
+  // The linearisation cache (BMPC_LIN_LDS; CVaR plans of a model with a description): A's varying
+  // entries, kept only while the launch that holds 16 egos per CU -- the rich one where it fits the
+  // 9,984 bytes without the cache, else the lean one -- still fits them with it (its tables in 16
+  // bits).  It lies behind the launch's other doubles, so a launch without it is sized as before.
+  lin_describe(desc, P.lin);
+  if (BMPC_LIN_LDS && desc.controller == BMPC_CTRL_CVAR && P.lin.na > 0 && P.tab16) {
+    const size_t budget = 1248 * sizeof(double);
+    const bool xf = desc.model == BMPC_MODEL_HIGHWAY_MERGE || (desc.flags & BMPC_PLAN_TRANSFORM);
+    const size_t eco = xf ? sizeof(double) * ECO_COUNT : 0;
+    const size_t tab = (sizeof(int16_t) * (size_t)P.ntab + 7) & ~(size_t)7;
+    const size_t lean = sizeof(double) * (size_t)P.nlds_lean + eco;
+    const size_t rich = lean + sizeof(double) * (size_t)(P.nsm * P.nsm) + tab;
+    const size_t base = rich <= budget ? rich : lean;
+    const size_t na = (size_t)P.lin.na * U;
+    if (base + sizeof(double) * na <= budget) P.nlin_a = (int)na;
+  }
+  P.nlds = P.nlds_rich + P.nlin_a;
+  if (P.nscr > 0 && P.nlds_rich > 1248) return "internal: the tree-solve LDS staging overflows the 16-egos-per-CU budget";
 
   // ---- weights -----------------------------------------------------------------------------
   double Qm[BMPC_MAX_N * BMPC_MAX_N], Rm[BMPC_MAX_D * BMPC_MAX_D];
@@ -360,18 +411,6 @@ std::string build_plan(const bmpc_plan_desc& desc, HostPlan& hp) {
       for (int r = 0; r < d; ++r) s += P.Wu[r * d + i] * P.Wu[r * d + j];
       P.RR[i * d + j] = s;
     }
-
-  // ---- concatenated tables -------------------------------------------------------------------
-#define BMPC_TOPO_HOSTVEC_(n) &hp.n,
-  std::vector<int32_t>* tabs[] = {BMPC_TOPO_FIELDS(BMPC_TOPO_HOSTVEC_)};   // same order as Topo
-#undef BMPC_TOPO_HOSTVEC_
-  hp.blob.clear();
-  hp.blob_off.clear();
-  for (auto* v : tabs) {
-    hp.blob_off.push_back(hp.blob.size());
-    hp.blob.insert(hp.blob.end(), v->begin(), v->end());
-  }
-  hp.point_tables(hp.blob.data());
 
   // ---- per-ego workspace layout --------------------------------------------------------------
   Layout& L = hp.lay;

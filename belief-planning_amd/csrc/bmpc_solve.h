@@ -142,7 +142,10 @@ BMPC_HD IpmResult solve_ego_ipm(const X& ex, const Plan& P, const Layout& L, Ego
   C.P = (CPlan*)&P;
   C.L = (CLayout*)&L;
   C.ws = (gdouble*)ws;
-  IpmResult r = ipm_solve<X, NX, NU>(ex, C);
+  // the linearisation cache of this solve (BMPC_LIN_LDS); a slab the model's description does
+  // not hold for ends the solve here
+  IpmResult r{EXIT_GUARD, 0, 0.0};
+  if (lin_fill<X, NX>(ex, *C.P, *C.L, C.ws)) r = ipm_solve<X, NX, NU>(ex, C);
   ipm_unpack<X, M>(ex, P, L, ws, r);
   return r;
 }

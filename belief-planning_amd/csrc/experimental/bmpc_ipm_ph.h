@@ -647,6 +647,7 @@ BMPC_HD IpmResult ipm_solve_phased(const X ex, const Ctx& C, double* lds_scratch
   auto run = [&](int ph, int it) {
     if (!ph_gate(st, ph)) return true;
     for (int i = P.nconst; i < nlds; ++i) lds_scratch[i] = 1.2345e300;   // nothing survives a kernel boundary
+    (void)lin_fill<X, NX>(ex, P, *C.L, C.ws);   // (a phase kernel with the cache would load it on entry; the guard was taken by the caller)
     return ph_run<X, NX, NU>(ex, C, ph, it);
   };
   run(PH_INIT1, 0);
@@ -676,7 +677,8 @@ BMPC_HD IpmResult solve_ego_ipm_phased(const X& ex, const Plan& P, const Layout&
   C.P = (CPlan*)&P;
   C.L = (CLayout*)&L;
   C.ws = (gdouble*)ws;
-  const IpmResult r = ipm_solve_phased<X, M::NX, M::NU>(ex, C, lds, nlds);
+  IpmResult r{EXIT_GUARD, 0, 0.0};
+  if (lin_fill<X, M::NX>(ex, *C.P, *C.L, C.ws)) r = ipm_solve_phased<X, M::NX, M::NU>(ex, C, lds, nlds);
   ipm_unpack<X, M>(ex, P, L, ws, r);
   return r;
 }

@@ -200,6 +200,10 @@ int bmpc_close(bmpc_ctx* ctx);
 int bmpc_plan_create(bmpc_ctx* ctx, const bmpc_plan_desc* desc, int batch, bmpc_plan** out);
 int bmpc_plan_destroy(bmpc_plan* plan);
 int bmpc_plan_info(const bmpc_plan* plan, int32_t* info /* [BMPC_INFO_COUNT] */);
+/* 1 if the solver kernel of the plan's last solve read A of the linearisation from its LDS cache
+ * (the CVaR IPM's one-wave kernels of the highway models, batches beyond 8 egos per compute unit
+ * on plans with room for it), else 0 */
+int bmpc_last_lin_cache(const bmpc_plan* plan);
 
 /* update_backup: policies[batch][m]; mask[batch] (NULL = all egos) */
 int bmpc_set_policies(bmpc_plan* plan, const bmpc_policy* policies, const uint8_t* mask);
